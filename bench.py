@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark: edges/s of the fused extrapolate -> update -> KL-clustering pass.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c2] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs
+DIR also writes what the last timed step computed (dump_outputs). Everything else described
+below -- the instrumented and inline-restore runs, rooflines, config 5, the C3 section, the
+other device stages, the CPU baselines, the drop-in stage -- runs only with --full.
 
 One step = one fused pass (gtf_pass: k_sender_scan, k_extrapolate, fused node
 kernel) over one synthetic TrackML-shaped event held in HBM. Every step processes
@@ -17,8 +22,8 @@ is uploaded with its nodes renumbered into the node kernel's schedule order tile
 by tile (--layout tiled, the default; "schedule" without tiles, "natural" keeps
 the host order).
 
-The K steps are timed twice, each run bracketed by barrier + synchronize: first
-as a caller runs them (value, ms_per_step), then with HIP events recorded before,
+The K steps are timed bracketed by barrier + synchronize: first as a caller runs
+them (value, ms_per_step), then (--full) again with HIP events recorded before,
 between and after the pass's kernels on their stream (kernel_ms, the roofline of
 the dominant kernel, instrumented_ms_per_step) -- every event record costs a few
 microseconds of GPU timeline, so it stays out of the headline.
@@ -911,121 +916,68 @@ def spawn_ranks(n):
     return rc
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--workload", default="c4", choices=["c2", "c3", "c4"])
-    ap.add_argument("--cpu-tracks", type=int, default=4000,
-                    help="tracks of the CPU baseline's secondary bounded sample (0: none)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-c5", action="store_true", help="skip the config-5 parabolic-KL section")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in stage wall time")
-    ap.add_argument("--no-c3", action="store_true",
-                    help="skip the configs[2] (C3) section beside the C4 headline (its launches have their own grid "
-                         "sizes: tools/kstats_by_grid.py separates them in a profiler's kernel trace)")
-    ap.add_argument("--layout", default="tiled", choices=["tiled", "padded", "schedule", "natural"],
-                    help="device node order (DeviceGraph layout)")
-    ap.add_argument("--tile", type=int, default=4096, help="nodes per tile of --layout tiled")
-    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo", "native"],
-                    help="collectives for N > 1: nccl = torch.distributed over RCCL (the default), native = "
-                         "libgtf's own RCCL communicator (gtf_comm_*, the id handed over torch.distributed; NOTE: "
-                         "it has never run with more than one rank -- the test box has one GPU -- so its grouped "
-                         "send / receive pairing at world > 1 is unverified on hardware), gloo = rehearsal with "
-                         "several ranks on one GPU")
-    args = ap.parse_args()
-    if args.gpus < 1:
-        ap.error("--gpus must be >= 1")
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # launched as `python bench.py --gpus N`: start the N ranks here, before anything
-        # touches the GPU, one child process per GPU (what torchrun would do)
-        sys.exit(spawn_ranks(args.gpus))
+DUMP_BUDGET = 64 * 1000 * 1000   # bytes of .npy payload --dump-outputs may write in all
+DUMP_SLOT_SAMPLE = 65536         # slots of the per-slot arrays kept when the whole arrays do not fit
+DUMP_SEED = 20240229
 
-    import torch
-    import torch.distributed as dist
-    from gtf import synth
-    from gtf.device import DeviceGraph
-    from gtf.params import Params
-    from gtf import roofline as rf
 
-    rank = int(os.environ.get("RANK", 0))
-    world = int(os.environ.get("WORLD_SIZE", 1))
-    local = int(os.environ.get("LOCAL_RANK", 0))
-    if args.backend == "gloo":   # rehearsal: ranks may share the GPU
-        local = local % max(torch.cuda.device_count(), 1)
-    torch.cuda.set_device(local)
-    dev = "cuda:%d" % local
-    if world != args.gpus:
-        raise SystemExit("bench.py: WORLD_SIZE=%d but --gpus %d" % (world, args.gpus))
-    if world > 1:
-        if args.backend in ("nccl", "native"):
-            dist.init_process_group("nccl", device_id=torch.device(dev))
-        else:   # rehearsal of the N > 1 path with several ranks on one GPU (RCCL needs one GPU per rank)
-            dist.init_process_group("gloo")
-        assert dist.get_world_size() == args.gpus, (dist.get_world_size(), args.gpus)
-
-    def barrier():
-        if world > 1:
-            dist.barrier()
-
-    p = Params()
-    g = synth.workload(args.workload, seed=1000 * rank)
-    # nodes renumbered on upload (DeviceGraph layout "tiled", the default): inside every
-    # run of 4096 nodes, bucketed by slot count, so each wavefront of the node kernel
-    # reads one contiguous run of slots while neighbouring hits stay close for the sender
-    # and extrapolation gathers; the results are the same bit for bit
-    # (tests/test_gpu_fullsize.py)
-    d = DeviceGraph(g, dev, layout=args.layout, tile=args.tile)
-    snap = d.snapshot(DeviceGraph.PASS_INPUTS)
-    K, W = args.steps, args.warmup
-    NE = 5
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(NE)] for _ in range(K)]
-    for row in evs:      # torch creates the HIP event on first record
-        for e in row:
-            e.record()
-    handles = [[e.cuda_event for e in row] for row in evs]
-
-    d.clear_errors()
-    for _ in range(W):
-        d.restore(snap)
-        d.full_pass(p)
-
-    d.stage_inputs(K)   # K resident copies of the pass input, one per timed step
-
-    def timed(instrumented, inline_restore=False):
-        """K steps bracketed by barrier + synchronize, step i on staged input copy i;
-        instrumented: a HIP event before, between and after the pass's kernels on their
-        stream (each event record is a few microseconds of GPU timeline, so the headline
-        pass is timed without them); inline_restore: one resident input restored by a
-        device copy before every pass instead (round-1 method, reported beside)"""
-        d.fill_inputs(snap)
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(K):
-            if inline_restore:
-                d.restore(snap)
-            else:
-                d.use_inputs(i)
-            d.full_pass(p, events=handles[i] if instrumented else None)
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        d.use_inputs(None)
-        return time.perf_counter() - t0
-
-    elapsed = timed(False)        # the headline: K passes as a caller runs them
-    elapsed_ev = timed(True)      # the same K passes with per-kernel events (kernel_ms, roofline)
-    elapsed_rs = timed(False, inline_restore=True)
+def dump_outputs(d, g, last, outdir):
+    """--dump-outputs: what the last timed step computed, as a caller receives it -- the host
+    TrackGraph DeviceGraph.download fills (every mutable per-node and per-slot array, host
+    order whatever the device layout), one DIR/<name>.npy each: float64 for the float and
+    32-bit integer fields, float32 for the 8-bit masks. Every written number is finite: the
+    host arrays hold NaN where the reference has no entry (an absent dict key, a node without
+    merged state), so a float field goes out as two files, <name>.npy with 0 in place of every
+    non-finite value and <name>_nonfinite.npy (float32) saying what stood there: 0 a finite
+    value, 1 NaN, 2 +inf, 3 -inf. Step `last` ran on staged input copy `last`, so that copy's
+    arena (the arrays a pass both reads and writes) is moved into the graph's own before the
+    download. The per-node arrays are written whole; of the per-slot arrays a fixed seeded
+    sample of rows (slot_sample_index.npy, ascending) when the whole would pass DUMP_BUDGET.
+    The event is seeded, so two builds write comparable files."""
+    from gtf.device import MUTABLE_NODE, STATIC_SLOT
+    from gtf.graph import SLOT_FIELDS
+    d.arena.copy_(d._staged[last][0])
+    gh = d.download(g.copy())
     flags = d.errors()
+    os.makedirs(outdir, exist_ok=True)
 
-    total_edges = float(g.n_edges)
-    tb = "gloo" if args.backend == "gloo" else "nccl"   # the torch.distributed group's backend
-    if world > 1:
-        elapsed = reduce_scalar(elapsed, dist.ReduceOp.MAX, dev, tb)
-        total_edges = reduce_scalar(total_edges, dist.ReduceOp.SUM, dev, tb)
+    def encode(name, a):
+        if a.dtype.kind != "f":
+            return {name: a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)}
+        kind = np.zeros(a.shape, np.float32)
+        kind[np.isnan(a)] = 1
+        kind[np.isposinf(a)] = 2
+        kind[np.isneginf(a)] = 3
+        return {name: np.where(kind == 0, a, 0.0).astype(np.float64), name + "_nonfinite": kind}
+
+    arrays = {}
+    for f in MUTABLE_NODE:
+        arrays.update(encode("node_" + f, gh.node[f]))
+    arrays["device_error_flags"] = np.array([flags], np.float64)
+    slot_fields = [f for f in SLOT_FIELDS if f not in STATIC_SLOT and f != "slot_key"]
+    row_bytes = 8 + sum(v.nbytes for f in slot_fields for v in encode(f, gh.slot[f][:1]).values())
+    room = DUMP_BUDGET - sum(a.nbytes for a in arrays.values()) - (1 << 16)   # (64 KiB: the .npy headers)
+    if row_bytes * g.n_slots <= room:
+        rows = np.arange(g.n_slots)
+    else:
+        n = min(DUMP_SLOT_SAMPLE, room // row_bytes)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(g.n_slots, size=n, replace=False))
+    arrays["slot_sample_index"] = rows.astype(np.float64)
+    for f in slot_fields:
+        arrays.update(encode("slot_" + f, gh.slot[f][rows]))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, total
+    assert all(np.isfinite(a).all() for a in arrays.values())
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "files": len(arrays), "bytes": int(total), "slots_sampled": int(rows.size),
+            "slots": int(g.n_slots)}
+
+
+def full_rooflines(args, d, g, evs, K, elapsed, dev, rank):
+    """--full: the per-kernel times of the instrumented run (evs: its HIP events) against the
+    byte models of SURVEY §8d, and the pass as a whole against the HBM peak"""
+    from gtf import roofline as rf
 
     def avg(a, b):
         return float(np.mean([evs[i][a].elapsed_time(evs[i][b]) for i in range(K)]))
@@ -1066,6 +1018,168 @@ def main():
     traffic = committed_traffic(args.workload, name, args.layout, args.tile, g.n_edges, g.n_nodes)
     pass_b = rf.pass_bytes(g.n_edges, g.n_nodes)
     copy_gbps = device_copy_gbps(dev) if rank == 0 else None
+    return {
+        "kernel_ms": {k: round(v[0], 5) for k, v in kern.items()},
+        "kernels_roofline": per_kernel,
+        "roofline": {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": rf.HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / rf.HBM_PEAK_GBS, "traffic": traffic,
+                     "algorithmic_bytes_per_launch": nbytes, "kernel_ms": ms,
+                     "device_copy_GBps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps if copy_gbps else None,
+                     "kl_eligible_nodes": int(elig.sum()), "kl_eligible_in_edges": e_elig,
+                     "byte_model": "SURVEY §8d (fused node kernel 89 B/edge + 186 B/node)",
+                     "builder_model_bytes_per_launch": builder.get(name),
+                     "builder_model_frac": per_kernel[name]["builder_model_frac"],
+                     "valu_roofline": per_kernel[name]["valu_roofline"]},
+        "pass_roofline": {"bound": "hbm", "algorithmic_bytes_per_step": pass_b,
+                          "byte_model": "SURVEY §8d B_alg = 183 E + 290 N",
+                          "achieved": pass_b / (elapsed / K) / 1e9, "peak": rf.HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": pass_b / (elapsed / K) / 1e9 / rf.HBM_PEAK_GBS},
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--workload", default="c4", choices=["c2", "c3", "c4"])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the instrumented and inline-restore runs of the same steps (kernel_ms, "
+                         "rooflines), the device copy bandwidth, config 5, the C3 section, the other device stages, "
+                         "the CPU baselines and the drop-in stage (each of them can be left out with its --no-* "
+                         "option). Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the host-order arrays "
+                         "DeviceGraph.download returns) as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--cpu-tracks", type=int, default=4000,
+                    help="tracks of the CPU baseline's secondary bounded sample (0: none)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-c5", action="store_true", help="--full without the config-5 parabolic-KL section")
+    ap.add_argument("--no-dropin", action="store_true", help="--full without the drop-in stage wall time")
+    ap.add_argument("--no-c3", action="store_true",
+                    help="--full without the configs[2] (C3) section beside the C4 headline (its launches have their "
+                         "own grid sizes: tools/kstats_by_grid.py separates them in a profiler's kernel trace)")
+    ap.add_argument("--layout", default="tiled", choices=["tiled", "padded", "schedule", "natural"],
+                    help="device node order (DeviceGraph layout)")
+    ap.add_argument("--tile", type=int, default=4096, help="nodes per tile of --layout tiled")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo", "native"],
+                    help="collectives for N > 1: nccl = torch.distributed over RCCL (the default), native = "
+                         "libgtf's own RCCL communicator (gtf_comm_*, the id handed over torch.distributed; NOTE: "
+                         "it has never run with more than one rank -- the test box has one GPU -- so its grouped "
+                         "send / receive pairing at world > 1 is unverified on hardware), gloo = rehearsal with "
+                         "several ranks on one GPU")
+    args = ap.parse_args()
+    if args.gpus < 1:
+        ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        # launched as `python bench.py --gpus N`: start the N ranks here, before anything
+        # touches the GPU, one child process per GPU (what torchrun would do)
+        sys.exit(spawn_ranks(args.gpus))
+
+    import torch
+    import torch.distributed as dist
+    from gtf import synth
+    from gtf.device import DeviceGraph
+    from gtf.params import Params
+
+    rank = int(os.environ.get("RANK", 0))
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    local = int(os.environ.get("LOCAL_RANK", 0))
+    if args.backend == "gloo":   # rehearsal: ranks may share the GPU
+        local = local % max(torch.cuda.device_count(), 1)
+    torch.cuda.set_device(local)
+    dev = "cuda:%d" % local
+    if world != args.gpus:
+        raise SystemExit("bench.py: WORLD_SIZE=%d but --gpus %d" % (world, args.gpus))
+    if world > 1:
+        if args.backend in ("nccl", "native"):
+            dist.init_process_group("nccl", device_id=torch.device(dev))
+        else:   # rehearsal of the N > 1 path with several ranks on one GPU (RCCL needs one GPU per rank)
+            dist.init_process_group("gloo")
+        assert dist.get_world_size() == args.gpus, (dist.get_world_size(), args.gpus)
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+
+    p = Params()
+    g = synth.workload(args.workload, seed=1000 * rank)
+    # nodes renumbered on upload (DeviceGraph layout "tiled", the default): inside every
+    # run of 4096 nodes, bucketed by slot count, so each wavefront of the node kernel
+    # reads one contiguous run of slots while neighbouring hits stay close for the sender
+    # and extrapolation gathers; the results are the same bit for bit
+    # (tests/test_gpu_fullsize.py)
+    d = DeviceGraph(g, dev, layout=args.layout, tile=args.tile)
+    snap = d.snapshot(DeviceGraph.PASS_INPUTS)
+    K, W = args.steps, args.warmup
+    full = args.full
+    NE = 5
+    evs = handles = None
+    if full:
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(NE)] for _ in range(K)]
+        for row in evs:      # torch creates the HIP event on first record
+            for e in row:
+                e.record()
+        handles = [[e.cuda_event for e in row] for row in evs]
+
+    d.clear_errors()
+    for _ in range(W):
+        d.restore(snap)
+        d.full_pass(p)
+
+    # C resident copies of the pass input, one per timed step: C = K while K copies fit in
+    # half of the free device memory (18 MB each on C4); a longer run times its K steps in
+    # runs of C, the copies refilled between the runs, outside the clock
+    C = K
+    if world == 1:
+        C = max(1, min(K, torch.cuda.mem_get_info()[0] // 2 // d.arena.numel()))
+    d.stage_inputs(C)
+
+    def timed(instrumented, inline_restore=False):
+        """K steps bracketed by barrier + synchronize, step i on staged input copy i;
+        instrumented: a HIP event before, between and after the pass's kernels on their
+        stream (each event record is a few microseconds of GPU timeline, so the headline
+        pass is timed without them); inline_restore: one resident input restored by a
+        device copy before every pass instead (round-1 method, reported beside)"""
+        total = 0.0
+        for lo in range(0, K, C):
+            d.fill_inputs(snap)
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(lo, min(lo + C, K)):
+                if inline_restore:
+                    d.restore(snap)
+                else:
+                    d.use_inputs(i - lo)
+                d.full_pass(p, events=handles[i] if instrumented else None)
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            total += time.perf_counter() - t0
+        d.use_inputs(None)
+        return total
+
+    elapsed = timed(False)        # the headline: K passes as a caller runs them
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(d, g, (K - 1) % C, args.dump_outputs)
+    flags = d.errors()
+    if full:
+        elapsed_ev = timed(True)      # the same K passes with per-kernel events (kernel_ms, roofline)
+        elapsed_rs = timed(False, inline_restore=True)
+        flags = d.errors()
+
+    total_edges = float(g.n_edges)
+    tb = "gloo" if args.backend == "gloo" else "nccl"   # the torch.distributed group's backend
+    if world > 1:
+        elapsed = reduce_scalar(elapsed, dist.ReduceOp.MAX, dev, tb)
+        total_edges = reduce_scalar(total_edges, dist.ReduceOp.SUM, dev, tb)
+
+    roof = full_rooflines(args, d, g, evs, K, elapsed, dev, rank) if full else {}
 
     sharded = None
     if world > 1:
@@ -1075,27 +1189,27 @@ def main():
             sharded = {"error": repr(ex)[:300]}
 
     c5 = comps = c5_sharded = None
-    if rank == 0 and world == 1 and not args.no_c5:
+    if full and rank == 0 and world == 1 and not args.no_c5:
         c5 = bench_c5(dev, K, W)
         comps = bench_components(g, p, dev)
-    if world > 1 and not args.no_c5:
+    if full and world > 1 and not args.no_c5:
         try:
             c5_sharded = bench_c5_sharded(dev, K, W, rank, world, tb)
         except Exception as ex:   # reported, the headline stands
             c5_sharded = {"error": repr(ex)[:300]}
 
     c3 = None
-    if rank == 0 and world == 1 and args.workload == "c4" and not args.no_c3:
+    if full and rank == 0 and world == 1 and args.workload == "c4" and not args.no_c3:
         try:
             c3 = bench_c3_section(dev, max(10, K // 5), 2, p, args.layout, args.tile)
         except Exception as ex:   # reported; the headline stands
             c3 = {"error": repr(ex)[:300]}
 
     cpu = cpu_cpp = dropin = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(g, p, args.cpu_tracks)
         cpu_cpp = cpu_baseline_cpp(g, p)
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if full and rank == 0 and world == 1 and not args.no_dropin:
         dropin = dropin_stage_wall(p)
 
     if rank == 0:
@@ -1107,12 +1221,11 @@ def main():
             "steps": K,
             "warmup": W,
             "ms_per_step": elapsed / K * 1e3,
-            "instrumented_ms_per_step": elapsed_ev / K * 1e3,
-            "ms_per_step_inline_restore": elapsed_rs / K * 1e3,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f64",
+            "full": full,
             "data": "synthetic (seeded TrackML-shaped generator, gtf/synth.py)",
             "config": {"workload": {"c4": "pileup-200 TrackML-shaped event (configs[3]) per GPU",
                                     "c3": "64 C2-like events fused into one CSR per GPU (configs[2])",
@@ -1120,29 +1233,16 @@ def main():
                        "nodes_per_gpu": g.n_nodes, "directed_edges_per_gpu": g.n_edges,
                        "parallelism": "event-parallel x%d (no collective)" % world, "layout": args.layout,
                        "pass": "gtf_pass: extrapolate (a6-a8) + update (a3,a9,a10x2,a11) + KL cluster (a12-a14)"},
-            "kernel_ms": {k: round(v[0], 5) for k, v in kern.items()},
-            "kernels_roofline": per_kernel,
-            "roofline": {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": rf.HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / rf.HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_launch": nbytes, "kernel_ms": ms,
-                         "device_copy_GBps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps if copy_gbps else None,
-                         "kl_eligible_nodes": int(elig.sum()), "kl_eligible_in_edges": e_elig,
-                         "byte_model": "SURVEY §8d (fused node kernel 89 B/edge + 186 B/node)",
-                         "builder_model_bytes_per_launch": builder.get(name),
-                         "builder_model_frac": per_kernel[name]["builder_model_frac"],
-                         "valu_roofline": per_kernel[name]["valu_roofline"]},
-            "pass_roofline": {"bound": "hbm", "algorithmic_bytes_per_step": pass_b,
-                              "byte_model": "SURVEY §8d B_alg = 183 E + 290 N",
-                              "achieved": pass_b / (elapsed / K) / 1e9, "peak": rf.HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": pass_b / (elapsed / K) / 1e9 / rf.HBM_PEAK_GBS},
-            "cpu_baseline": cpu,
-            "cpu_baseline_cpp": cpu_cpp,
-            "dropin_stage": dropin,
             "device_error_flags": flags,
-            "c5_parabolic_kl": c5,
-            "c3_fused_batch": c3,
-            "other_path_stages": comps,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if full:   # everything beside the headline
+            out["instrumented_ms_per_step"] = elapsed_ev / K * 1e3
+            out["ms_per_step_inline_restore"] = elapsed_rs / K * 1e3
+            out.update(roof)
+            out.update({"cpu_baseline": cpu, "cpu_baseline_cpp": cpu_cpp, "dropin_stage": dropin,
+                        "c5_parabolic_kl": c5, "c3_fused_batch": c3, "other_path_stages": comps})
         if c5_sharded is not None:
             out["c5_event_sharded"] = c5_sharded
         if world > 1:
@@ -1163,8 +1263,9 @@ def main():
                 out["config"]["event_directed_edges"] = sharded["edges"]
                 # the roofline of the headline: rank 0's kernels of the sharded pass (the replica
                 # pass's roofline stays under event_replicas)
-                replicas["roofline"] = out["roofline"]
-                replicas["kernel_ms"] = out["kernel_ms"]
+                if full:
+                    replicas["roofline"] = out["roofline"]
+                    replicas["kernel_ms"] = out["kernel_ms"]
                 out["roofline"] = sharded["roofline"]
                 out["kernel_ms"] = sharded["roofline"]["kernel_ms_all"]
                 # the N = 1 -> N speed-up of the single event: measured (this GPU's own one-event

@@ -19,7 +19,7 @@ run_env() {   # variant spec -> "env A=B C=D"
 for r in $(seq 1 $ROUNDS); do
   for spec in "$@"; do
     name=${spec%%=*}
-    (cd /tmp && env $(run_env $spec) timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/$name.$r -o run --output-format csv -- python3 $R/bench.py --no-cpu --no-c5 --no-dropin --no-c3 --steps 30 --warmup 3 > $OUT/$name.$r.json 2> $OUT/$name.$r.err) || { echo "FAIL $name"; tail -5 $OUT/$name.$r.err; exit 1; }
+    (cd /tmp && env $(run_env $spec) timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/$name.$r -o run --output-format csv -- python3 $R/bench.py --full --no-cpu --no-c5 --no-dropin --no-c3 --steps 30 --warmup 3 > $OUT/$name.$r.json 2> $OUT/$name.$r.err) || { echo "FAIL $name"; tail -5 $OUT/$name.$r.err; exit 1; }
     python3 $R/tools/kstats.py $OUT/$name.$r $name
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('   ', sys.argv[2], 'ms/step', round(d['ms_per_step'],5), {k[:12]: round(v*1e3,1) for k,v in d['kernel_ms'].items()})" $OUT/$name.$r.json $name
   done

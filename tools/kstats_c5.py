@@ -1,4 +1,4 @@
-"""Config 5's k_parabolic_kl launches of a rocprofv3 --kernel-trace run of bench.py, split
+"""Config 5's k_parabolic_kl launches of a rocprofv3 --kernel-trace run of bench.py --full, split
 into the warm-up, the cold rotation (the roofline figure of the bench line) and the hot
 relaunches of one batch, by their order in the trace and the launch_sequence the bench
 line records per dtype (rocprofv3 --stats averages all of them together).
