@@ -1,5 +1,5 @@
 // gtf_node_group.h -- the node-local op sequence with G lanes per receiver node
-// (G = 4, 8, 16, 32, 64 for nodes with <= 4, 8, 16, 32, 64 slots), one slot per lane.
+// (G = 2, 4, 6, 8, 12, 16, 32, 64 for nodes with at most that many slots), one slot per lane.
 //
 // Why: every stage after message passing reduces over one node's in-edge slot
 // segment. One thread per node serialises O(d^2) loops over
@@ -51,16 +51,30 @@ __device__ __forceinline__ T bperm(int addr, T x) {
     }
 }
 
+// G = 6 and 12: 10 and 5 groups per wavefront at lanes [gbase, gbase + G), gbase a multiple of
+// G (lanes 60..63 hold no group and leave before the loads). Such a group is not aligned to a
+// power of two, so its shuffles address wave lane gbase + src through ds_bpermute, and an xor
+// butterfly would leave it: the reductions take cyclic steps instead -- lane gl reads group
+// lane (gl + o) % G for o = 1, 2, 4 (, 8), after which it holds the windows [gl, gl + 8) or
+// [gl, gl + 16) mod G, the whole group. max, min and or are idempotent and exact, so the
+// overlap changes nothing, and the step count is that of 8 and 16 lanes.
 template <int G>
 struct Grp {
+    static constexpr bool P2 = (G & (G - 1)) == 0;          // lanes [gbase, gbase + G) aligned to G
+    static constexpr int HI = P2 ? G / 2 : (G > 8 ? 8 : 4);   // first (largest) reduction step
     int gl;     // lane within the group
     int gbase;  // first wave lane of the group
     int lane4;  // 4 x the wave lane (ds_bpermute byte address of this lane)
     __device__ __forceinline__ Grp() {
         int tid = (int)threadIdx.x;
         const int lane = tid & 63;
-        gl = lane & (G - 1);
-        gbase = lane & ~(G - 1);
+        if constexpr (P2) {
+            gl = lane & (G - 1);
+            gbase = lane & ~(G - 1);
+        } else {
+            gl = lane % G;
+            gbase = lane - gl;
+        }
         lane4 = lane << 2;
     }
     __device__ __forceinline__ unsigned long long bits(bool pred) const {
@@ -70,35 +84,46 @@ struct Grp {
     }
     __device__ __forceinline__ int count(bool pred) const { return __popcll(bits(pred)); }
     __device__ __forceinline__ bool any(bool pred) const { return bits(pred) != 0ull; }
-#if GTF_FAST_SHFL
     template <typename T>
-    __device__ __forceinline__ T shfl(T x, int src) const { return bperm<T>((gbase + src) << 2, x); }
+    __device__ __forceinline__ T shfl(T x, int src) const {
+        if constexpr (!P2 || GTF_FAST_SHFL) return bperm<T>((gbase + src) << 2, x);
+        else return __shfl(x, src, G);
+    }
+    // one reduction step: the xor partner, or the cyclic one of a 6- / 12-lane group
     template <typename T>
-    __device__ __forceinline__ T xshfl(T x, int o) const { return bperm<T>(lane4 ^ (o << 2), x); }
-#else
-    template <typename T>
-    __device__ __forceinline__ T shfl(T x, int src) const { return __shfl(x, src, G); }
-    template <typename T>
-    __device__ __forceinline__ T xshfl(T x, int o) const { return __shfl_xor(x, o, G); }
-#endif
+    __device__ __forceinline__ T xshfl(T x, int o) const {
+        if constexpr (!P2) {
+            // (the partner's address through an opaque copy of gl: computed where it is used, 4
+            // VALU instructions, instead of one register per step held across the clustering's
+            // loops -- the kernel has none to spare)
+            int l = gl;
+            asm volatile("" : "+v"(l));
+            const unsigned t = (unsigned)(l + o);
+            return bperm<T>((gbase + (int)min(t, t - (unsigned)G)) << 2, x);
+        } else if constexpr (GTF_FAST_SHFL) {
+            return bperm<T>(lane4 ^ (o << 2), x);
+        } else {
+            return __shfl_xor(x, o, G);
+        }
+    }
     __device__ __forceinline__ int max_i(int x) const {
 #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) x = max(x, xshfl(x, o));
+        for (int o = HI; o > 0; o >>= 1) x = max(x, xshfl(x, o));
         return x;
     }
     __device__ __forceinline__ int min_i(int x) const {
 #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) x = min(x, xshfl(x, o));
+        for (int o = HI; o > 0; o >>= 1) x = min(x, xshfl(x, o));
         return x;
     }
     __device__ __forceinline__ double min_d(double x) const {  // NaN-free inputs
 #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) x = fmin(x, xshfl(x, o));
+        for (int o = HI; o > 0; o >>= 1) x = fmin(x, xshfl(x, o));
         return x;
     }
     __device__ __forceinline__ unsigned or_u(unsigned x) const {
 #pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) x |= xshfl(x, o);
+        for (int o = HI; o > 0; o >>= 1) x |= xshfl(x, o);
         return x;
     }
     __device__ __forceinline__ int size() const { return G; }
@@ -282,7 +307,7 @@ __device__ __forceinline__ double ordered_sum(NodeCtx<G>& c, double* sval, LaneD
     // the line is read CH entries at a time (independent LDS reads, one wait) and added in
     // order; entries past the last key add +0.0, which leaves the sum unchanged (it is never
     // -0.0: it starts at +0.0 and round-to-nearest cancellation gives +0.0)
-    constexpr int CH = G == 0 ? 1 : (G < 8 ? G : 8);   // chunks stay inside the group's line
+    constexpr int CH = G == 0 ? 1 : (G == 6 || G == 12 ? 6 : (G < 8 ? G : 8));   // CH divides G: chunks stay inside the group's line
     for (int i = 0; i < npres; i += CH) {
         double v[CH];
 #pragma unroll
@@ -934,16 +959,20 @@ __device__ __forceinline__ void g_cluster(NodeCtx<G>& c, gtf_nodes& n, const gtf
 }
 
 // LDS of one wavefront's clustering stages: the largest (64 / G) x sizeof(StageT<G>) over the
-// group sizes (G = 2: 32 stages of 216 bytes; every other G: 6,784 bytes). Every wave's stages
+// group sizes (G = 2: 32 stages of 216 bytes; G = 6 and 12: 10 and 5 stages, 6,400 and 6,360
+// bytes; every other G: 6,784 bytes). Every wave's stages
 // start at a multiple of this span whatever its G, so waves of one block that run different
 // group sizes can never overlap each other's stages (round-5 verdict item 1).
 template <int G>
 constexpr size_t wave_stage_bytes() { return (size_t)(64 / G) * sizeof(StageT<G>); }
 constexpr size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 constexpr size_t WAVE_STAGE_BYTES =
-    max_sz(max_sz(max_sz(wave_stage_bytes<2>(), wave_stage_bytes<4>()), max_sz(wave_stage_bytes<8>(), wave_stage_bytes<16>())),
-           max_sz(wave_stage_bytes<32>(), wave_stage_bytes<64>()));
+    max_sz(max_sz(max_sz(max_sz(wave_stage_bytes<2>(), wave_stage_bytes<4>()), max_sz(wave_stage_bytes<8>(), wave_stage_bytes<16>())),
+                  max_sz(wave_stage_bytes<32>(), wave_stage_bytes<64>())),
+           max_sz(wave_stage_bytes<6>(), wave_stage_bytes<12>()));   // (10 and 5 stages: 6,400 and 6,360 bytes)
 static_assert(WAVE_STAGE_BYTES % 8 == 0, "stage spans keep 8-byte alignment");
+static_assert(wave_stage_bytes<6>() <= wave_stage_bytes<8>() && wave_stage_bytes<12>() <= wave_stage_bytes<8>(),
+              "the 6- and 12-lane stages fit the span of the power-of-two groups");
 constexpr size_t node_smem_bytes() { return NBLOCK * sizeof(double) + (NBLOCK / 64) * WAVE_STAGE_BYTES; }
 // this lane's group's stage: the wave's own span, then the group's entry in it
 template <typename Stage, int G>
@@ -1261,7 +1290,16 @@ __device__ __forceinline__ void node_seq_body(const gtf_graph& g, gtf_nodes& n, 
     using Q = OpSeq<OPS...>;
     using Stage = StageT<G>;
     NodeCtx<G> c;
-    const int gi = (bid * NBLOCK + (int)threadIdx.x) / G;
+    int gi;
+    if constexpr (Grp<G>::P2) {
+        gi = (bid * NBLOCK + (int)threadIdx.x) / G;
+    } else {
+        // 64 / G whole groups per wavefront: the group index counts per wave, and the wave's
+        // last lanes (60..63) hold no group
+        constexpr int GPW = 64 / G;
+        if (c.grp.gbase >= GPW * G) return;
+        gi = (bid * (NBLOCK / 64) + (int)threadIdx.x / 64) * GPW + c.grp.gbase / G;
+    }
 #if GTF_OP_TIMING
     const uint64_t t_start = __builtin_readcyclecounter();
     const uint64_t rt_start = __builtin_amdgcn_s_memrealtime();   // chip-wide constant-rate clock
@@ -1321,12 +1359,16 @@ __device__ __forceinline__ void node_seq_body(const gtf_graph& g, gtf_nodes& n, 
 #endif
 }
 
+constexpr int NBUCKET = 8;
+constexpr int BUCKET_G[NBUCKET] = {64, 32, 16, 12, 8, 6, 4, 2};   // lanes per node, slowest first
+// nodes per block of a G-lane bucket: 64 / G whole groups in each of the block's wavefronts
+constexpr int bucket_nodes_per_block(int G) { return (NBLOCK / 64) * (64 / G); }
 struct Buckets {
-    const int32_t* list[6];  // node lists for G = 64, 32, 16, 8, 4, 2 (slowest first)
-    const int32_t* seg[6];   // their slot segments (gtf_graph.sched_seg) or NULL
-    int32_t count[6];
-    int32_t blocks[6];
-    Arith ar[6];             // padded tile layout (ar[q].c > 0: addresses by arithmetic)
+    const int32_t* list[NBUCKET];  // node lists for G = BUCKET_G
+    const int32_t* seg[NBUCKET];   // their slot segments (gtf_graph.sched_seg) or NULL
+    int32_t count[NBUCKET];
+    int32_t blocks[NBUCKET];
+    Arith ar[NBUCKET];             // padded tile layout (ar[q].c > 0: addresses by arithmetic)
 };
 
 // All arguments of k_node_multi in one by-value struct (the kernarg segment).
@@ -1343,7 +1385,7 @@ struct NodeKArgs {
 typedef const __attribute__((address_space(4))) NodeKArgs* KArgPtr;
 
 // The kernarg segment through an opaque copy of its address: the compiler cannot hoist the
-// argument loads of the six bucket bodies into the kernel's entry (they are speculatable
+// argument loads of the eight bucket bodies into the kernel's entry (they are speculatable
 // kernarg loads otherwise), where their union -- ~90 SGPRs of pointers live across the
 // whole op sequence -- spilled 64 SGPRs into VGPR lanes on every wave. Each body now loads
 // only its own arguments, where it uses them (scalar loads from the constant segment).
@@ -1403,31 +1445,23 @@ __global__ void __launch_bounds__(NBLOCK) GTF_NODE_WAVES_ATTR k_node_multi(NodeK
     node_tables_init();
     __syncthreads();
     int b = node_block_map<GTF_NODE_XCD_CHUNK>((int)blockIdx.x, (int)gridDim.x);
-#ifndef GTF_NODE_ORDER
-#define GTF_NODE_ORDER 0   // 1 (diagnostics): the buckets by measured wave life, longest first (16, 32, 8, 64, 4, 2)
-#endif
-#if GTF_NODE_ORDER == 1
-    if (b < A->bk.blocks[2]) { node_bucket<16, OPS...>(2, b, smem); return; }
-    b -= A->bk.blocks[2];
-    if (b < A->bk.blocks[1]) { node_bucket<32, OPS...>(1, b, smem); return; }
-    b -= A->bk.blocks[1];
-    if (b < A->bk.blocks[3]) { node_bucket<8, OPS...>(3, b, smem); return; }
-    b -= A->bk.blocks[3];
-    if (b < A->bk.blocks[0]) { node_bucket<64, OPS...>(0, b, smem); return; }
-    b -= A->bk.blocks[0];
-#else
+    // (BUCKET_G order; the 12- and 6-lane buckets are the 9..12- and 5..6-slot nodes split
+    // off the 16- and 8-lane ones, gtf_graph.n_g12 / n_g6)
     if (b < A->bk.blocks[0]) { node_bucket<64, OPS...>(0, b, smem); return; }
     b -= A->bk.blocks[0];
     if (b < A->bk.blocks[1]) { node_bucket<32, OPS...>(1, b, smem); return; }
     b -= A->bk.blocks[1];
     if (b < A->bk.blocks[2]) { node_bucket<16, OPS...>(2, b, smem); return; }
     b -= A->bk.blocks[2];
-    if (b < A->bk.blocks[3]) { node_bucket<8, OPS...>(3, b, smem); return; }
+    if (b < A->bk.blocks[3]) { node_bucket<12, OPS...>(3, b, smem); return; }
     b -= A->bk.blocks[3];
-#endif
-    if (b < A->bk.blocks[4]) { node_bucket<4, OPS...>(4, b, smem); return; }
+    if (b < A->bk.blocks[4]) { node_bucket<8, OPS...>(4, b, smem); return; }
     b -= A->bk.blocks[4];
-    node_bucket<2, OPS...>(5, b, smem);
+    if (b < A->bk.blocks[5]) { node_bucket<6, OPS...>(5, b, smem); return; }
+    b -= A->bk.blocks[5];
+    if (b < A->bk.blocks[6]) { node_bucket<4, OPS...>(6, b, smem); return; }
+    b -= A->bk.blocks[6];
+    node_bucket<2, OPS...>(7, b, smem);
 }
 
 // GTF_SPLIT_G2 (A/B): the <= 2-slot bucket in a launch of its own after the others, at
@@ -1444,7 +1478,7 @@ __global__ void __launch_bounds__(NBLOCK) __attribute__((amdgpu_waves_per_eu(GTF
     __shared__ __attribute__((aligned(16))) char smem[NBLOCK * sizeof(double)];
     node_tables_init();
     __syncthreads();
-    node_bucket<2, OPS...>(5, node_block_map<GTF_NODE_XCD_CHUNK>((int)blockIdx.x, (int)gridDim.x), smem);
+    node_bucket<2, OPS...>(NBUCKET - 1, node_block_map<GTF_NODE_XCD_CHUNK>((int)blockIdx.x, (int)gridDim.x), smem);
 }
 
 // Packed lane segments (gtf_graph.pack_ent / pack_wave): wavefront wv takes the entries

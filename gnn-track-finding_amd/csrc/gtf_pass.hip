@@ -1200,11 +1200,18 @@ int launch_seq(const gtf_graph* g, gtf_nodes* n, gtf_states* tse, gtf_states* ut
             Buckets bk;
             // the first n_g2 entries of the <= 4-slot bucket have <= 2 slots: 2 lanes each
             const int n2 = g->n_g2 > 0 && g->n_g2 <= g->n_g4 ? g->n_g2 : 0;
-            const int cnt[6] = {g->n_g64, g->n_g32, g->n_g16, g->n_g8, g->n_g4 - n2, n2};
-            const int gs[6] = {64, 32, 16, 8, 4, 2};
+            // likewise the first n_g6 / n_g12 entries of the <= 8- / <= 16-slot buckets have <= 6 /
+            // <= 12 slots: 6 / 12 lanes each (the padded tiles give every node of a group its
+            // full lane count of slots: no sub-buckets there)
+            const int n6 = g->pad_tiles == 0 && g->n_g6 > 0 && g->n_g6 <= g->n_g8 ? g->n_g6 : 0;
+            const int n12 = g->pad_tiles == 0 && g->n_g12 > 0 && g->n_g12 <= g->n_g16 ? g->n_g12 : 0;
+            const int cnt[NBUCKET] = {g->n_g64, g->n_g32, g->n_g16 - n12, n12, g->n_g8 - n6, n6, g->n_g4 - n2, n2};
             const int32_t* s8 = g->sched + g->n_g4;
-            const int32_t* starts[6] = {s8 + g->n_g8 + g->n_g16 + g->n_g32, s8 + g->n_g8 + g->n_g16, s8 + g->n_g8,
-                                        s8, g->sched + n2, g->sched};
+            const int32_t* s16 = s8 + g->n_g8;
+            const int32_t* starts[NBUCKET] = {s16 + g->n_g16 + g->n_g32, s16 + g->n_g16, s16 + n12, s16,
+                                              s8 + n6, s8, g->sched + n2, g->sched};
+            // a bucket's group in the padded tile layout (pad_count: G = 2, 4, 8, 16, 32, 64)
+            const int padj[NBUCKET] = {5, 4, 3, -1, 2, -1, 1, 0};
             int total = 0;
             // padded tile layout: tile offsets of the groups G = 2, 4, 8, 16, 32, 64 (in that order)
             int noff[6] = {0}, soff[6] = {0};
@@ -1212,29 +1219,30 @@ int launch_seq(const gtf_graph* g, gtf_nodes* n, gtf_states* tse, gtf_states* ut
                 noff[j] = noff[j - 1] + g->pad_count[j - 1];
                 soff[j] = soff[j - 1] + g->pad_count[j - 1] * (2 << (j - 1));
             }
-            for (int q = 0; q < 6; q++) {
+            for (int q = 0; q < NBUCKET; q++) {
                 bk.list[q] = starts[q];
                 bk.seg[q] = g->sched_seg ? g->sched_seg + 2 * (starts[q] - g->sched) : nullptr;
                 bk.count[q] = cnt[q];
                 bk.ar[q] = Arith{0, 0, 0, 0, 0};
-                if (g->pad_tiles > 0) {   // every node of the group, in tile order, by arithmetic
-                    const int j = 5 - q;
+                if (g->pad_tiles > 0 && padj[q] >= 0) {   // every node of the group, in tile order, by arithmetic
+                    const int j = padj[q];
                     bk.ar[q] = Arith{g->pad_count[j], noff[j], soff[j], g->pad_tile_nodes, g->pad_tile_slots};
                     bk.count[q] = g->pad_tiles * g->pad_count[j];
                 }
-                bk.blocks[q] = (bk.count[q] + NBLOCK / gs[q] - 1) / (NBLOCK / gs[q]);
+                const int per = bucket_nodes_per_block(BUCKET_G[q]);
+                bk.blocks[q] = (bk.count[q] + per - 1) / per;
                 total += bk.blocks[q];
             }
             if (g->pack_ent && g->pack_wave && g->n_pack_waves > 0)   // every <= 64-slot node, packed
                 hipLaunchKernelGGL((k_node_pack<OPS...>), dim3((g->n_pack_waves + NBLOCK / 64 - 1) / (NBLOCK / 64)),
                                    dim3(NBLOCK), 0, st, *g, *n, T, U, *e, *p, w, chi2, kl);
-            else if (GTF_SPLIT_G2 && bk.blocks[5] > 0) {   // (A/B) the <= 2-slot bucket in a launch of its own
-                const int b5 = bk.blocks[5];
-                bk.blocks[5] = 0;
+            else if (GTF_SPLIT_G2 && bk.blocks[NBUCKET - 1] > 0) {   // (A/B) the <= 2-slot bucket in a launch of its own
+                const int b5 = bk.blocks[NBUCKET - 1];
+                bk.blocks[NBUCKET - 1] = 0;
                 if (total - b5 > 0)
                     hipLaunchKernelGGL((k_node_multi<OPS...>), dim3(total - b5), dim3(NBLOCK), 0, st,
                                        NodeKArgs{*g, *n, T, U, *e, *p, w, chi2, kl, bk});
-                bk.blocks[5] = b5;
+                bk.blocks[NBUCKET - 1] = b5;
                 hipLaunchKernelGGL((k_node_g2<OPS...>), dim3(b5), dim3(NBLOCK), 0, st,
                                    NodeKArgs{*g, *n, T, U, *e, *p, w, chi2, kl, bk});
             } else if (total > 0)

@@ -16,7 +16,7 @@ F64 = ctypes.c_double
 
 
 U32 = ctypes.c_uint32
-ABI_VERSION = 7   # GTF_ABI_VERSION of include/gtf.h
+ABI_VERSION = 8   # GTF_ABI_VERSION of include/gtf.h
 
 
 class GtfGraph(ctypes.Structure):
@@ -32,7 +32,7 @@ class GtfGraph(ctypes.Structure):
                 ("pack_ent", P), ("pack_wave", P), ("n_pack_waves", I32), ("out_lanes", P),
                 ("pad_tiles", I32), ("pad_tile_nodes", I32), ("pad_tile_slots", I32), ("pad_count", I32 * 6),
                 ("pad_reserved_", I32), ("slot_outidx", P), ("slot_class", P), ("slot_sflags", P),
-                ("slot_sxzr", P), ("slot_static", P), ("slot_xclass", P)]
+                ("slot_sxzr", P), ("slot_static", P), ("slot_xclass", P), ("n_g6", I32), ("n_g12", I32)]
 
     def __init__(self, **fields):
         super().__init__(**fields)

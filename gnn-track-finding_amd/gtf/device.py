@@ -206,6 +206,26 @@ def schedule_order(slot_ptr, tile=0):
     return np.lexsort((idx, bucket, t))
 
 
+def node_schedule(slot_ptr):
+    """(sched, bucket sizes [n_g4, n_g8, n_g16, n_g32, n_g64], n_big, (n_g2, n_g6, n_g12)): the
+    slot-count-bucketed node schedule of the node-local kernels (gtf_graph.sched: G lanes per
+    node), node order inside a bucket except that the nodes of a narrower lane group come
+    first -- the <= 2-slot nodes in the <= 4-slot bucket (2 lanes, n_g2), the <= 6-slot ones
+    in the <= 8-slot bucket (6 lanes, n_g6) and the <= 12-slot ones in the <= 16-slot bucket
+    (12 lanes, n_g12); then the nodes beyond 64 slots (one thread each)"""
+    deg = np.diff(np.asarray(slot_ptr, dtype=np.int64))
+    idx = np.arange(deg.size, dtype=np.int32)
+    buckets = [idx[(deg >= lo) & (deg <= hi)] for lo, hi in BUCKETS]
+    sub = []
+    for q, narrow in ((0, 2), (1, 6), (2, 12)):
+        first = deg[buckets[q]] <= narrow
+        buckets[q] = np.concatenate([buckets[q][first], buckets[q][~first]])
+        sub.append(int(first.sum()))
+    rest = idx[deg > 64]
+    sched = np.concatenate(buckets + [rest]).astype(np.int32)
+    return sched, [int(b.size) for b in buckets], int(rest.size), tuple(sub)
+
+
 TILE = 4096   # nodes per tile of the "tiled" layout
 
 
@@ -304,14 +324,8 @@ class DeviceGraph:
             solo = np.zeros(0, np.uint8)
         up("solo", solo)
         # slot-count-bucketed node schedule for the node-local kernels (G lanes per node)
-        deg = np.diff(g.slot_ptr.astype(np.int64))
-        idx = np.arange(g.n_nodes, dtype=np.int32)
-        buckets = [idx[(deg >= lo) & (deg <= hi)] for lo, hi in BUCKETS]
-        # the <= 2-slot nodes first in the <= 4-slot bucket: they run on 2 lanes (gtf_graph.n_g2)
-        buckets[0] = np.concatenate([buckets[0][deg[buckets[0]] <= 2], buckets[0][deg[buckets[0]] > 2]])
-        self.n_g2 = int((deg[buckets[0]] <= 2).sum())
-        rest = idx[deg > 64]
-        sched = np.concatenate(buckets + [rest]).astype(np.int32)
+        sched, self.n_g_all, self.n_big, sub = node_schedule(g.slot_ptr)
+        self.n_g2, self.n_g6, self.n_g12 = sub
         up("sched", sched)
         up("sched_seg", sched_segments(g.slot_ptr, sched))
         osched, self.n_o = sender_schedule(g.out_ptr)
@@ -323,8 +337,6 @@ class DeviceGraph:
             up("pack_ent", pent)
             up("pack_wave", pwave)
             self.n_pack_waves = int(pwave.size - 1)
-        self.n_g_all = [int(b.size) for b in buckets]
-        self.n_big = int(rest.size)
         self.n_g = self.n_g_all if schedule else [0] * len(BUCKETS)
         self.use_sched = schedule
         for f in ("gnn", "xyzr", "layer") + MUTABLE_NODE:
@@ -409,7 +421,7 @@ class DeviceGraph:
         sched = dict(n_big=self.n_big, sched=p("sched"), n_g4=self.n_g_all[0], n_g8=self.n_g_all[1],
                      n_g16=self.n_g_all[2], n_g32=self.n_g_all[3], n_g64=self.n_g_all[4], sched_seg=p("sched_seg"),
                      out_sched=p("out_sched"), n_o4=self.n_o[0], n_o8=self.n_o[1], n_o16=self.n_o[2],
-                     n_g2=self.n_g2, out_lanes=p("out_lanes"))
+                     n_g2=self.n_g2, out_lanes=p("out_lanes"), n_g6=self.n_g6, n_g12=self.n_g12)
         if self.pad_plan is not None and self.pad_plan["tile_nodes"] > 0:   # (an empty graph has no tiles)
             pl = self.pad_plan
             sched.update(pad_tiles=pl["tiles"], pad_tile_nodes=pl["tile_nodes"], pad_tile_slots=pl["tile_slots"],

@@ -46,7 +46,7 @@ typedef void* gtf_stream_t; /* a hipStream_t */
 /* Version of the struct layouts below. gtf_graph carries it with its own size, and every
  * entry point taking a gtf_graph refuses a caller built against another layout
  * (status -3, gtf_last_error() names both). Bumped on every layout change. */
-#define GTF_ABI_VERSION 7u
+#define GTF_ABI_VERSION 8u
 
 /* ---- graph structure (read-only on the path) ------------------------------ */
 typedef struct gtf_graph {
@@ -163,6 +163,13 @@ typedef struct gtf_graph {
      * their classes too instead of electing leaders per distinct value; 0 elsewhere. [S], or
      * NULL. */
     const uint64_t* slot_xclass;
+    /* optional (v8): sub-buckets of the schedule for gtf_pass's fused node kernel. The first n_g6
+     * entries of the n_g8 bucket have <= 6 slots and run on 6 lanes per node (10 nodes per
+     * wavefront instead of 8); the first n_g12 entries of the n_g16 bucket have <= 12 slots and
+     * run on 12 lanes (5 nodes per wavefront instead of 4). 0 = the whole bucket on 8 / 16
+     * lanes. The other entry points take the buckets whole. */
+    int32_t n_g6;
+    int32_t n_g12;
 } gtf_graph;
 
 /* ---- per-node mutable state ------------------------------------------------ */
