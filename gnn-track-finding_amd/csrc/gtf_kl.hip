@@ -22,6 +22,10 @@
 // committed training CSV this matches to 8e-11 relative (tests/test_kat_parabolic.py).
 // sv[2] = 0 and cov[2][2] = s1 for every state, so the KL terms of component 2
 // vanish and a state is 7 numbers in LDS: sv0, sv1, c00, c11, i00, i01, i11.
+//
+// Two coordinate sources share the kernels (the paths below): gtf_parabolic_kl reads fp64
+// rows and int64 truth ids; gtf_parabolic_kl_q32 reads 32-bit fixed-point coordinates and
+// int32 ids, half the bytes per node, and computes in fp32 throughout.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -65,14 +69,6 @@ __device__ __forceinline__ Frame node_frame_xy(double x, double y) {
     return f;
 }
 
-// GNN_Measurement x / y of node v: rows of gnn_stride doubles (4: x, y, z, r; 2: the
-// compact x, y copy, half the bytes of the four-field rows)
-__device__ __forceinline__ int64_t gnn_row(const gtf_kl_graph& g, int v) {
-    return (int64_t)(g.gnn_stride ? g.gnn_stride : 4) * v;
-}
-__device__ __forceinline__ double gx(const gtf_kl_graph& g, int v) { return g.gnn[gnn_row(g, v)]; }
-__device__ __forceinline__ double gy(const gtf_kl_graph& g, int v) { return g.gnn[gnn_row(g, v) + 1]; }
-
 // cache policy of the once-touched streams (GTF_KL_NT bits, diagnostics builds): 1 the
 // outputs stored non-temporal, 2 the in-edge sender lists loaded non-temporal, 4 the node's
 // own coordinates and truth id too (they are also other nodes' sender gathers)
@@ -95,49 +91,11 @@ __device__ __forceinline__ T ld_own(const T* p) {
     return *p;
 }
 
-// where a kernel reads neighbour coordinates and truth ids: global memory, or a block's
-// LDS window of consecutive nodes [lo, hi) with global memory beyond it
-struct GSrc {   // the fields themselves, not a pointer to the kernel-argument struct
-    const double* gnn;
-    int64_t stride;
-    const int64_t* truth;
-    __device__ __forceinline__ explicit GSrc(const gtf_kl_graph& g)
-        : gnn(g.gnn), stride(g.gnn_stride ? g.gnn_stride : 4), truth(g.truth) {}
-    __device__ __forceinline__ double x(int u) const { return gnn[stride * u]; }
-    __device__ __forceinline__ double y(int u) const { return gnn[stride * u + 1]; }
-    __device__ __forceinline__ long long t(int u) const { return truth[u]; }
-};
-struct WSrc {
-    const gtf_kl_graph* g;
-    const double* sx;
-    const double* sy;
-    const long long* st;
-    int lo, hi;
-    __device__ __forceinline__ bool in(int u) const { return u >= lo && u < hi; }
-    // the LDS read at a clamped index always, the global one only outside the window: a
-    // select of values (a select of an LDS and a global address miscompiles on gfx950)
-    __device__ __forceinline__ int at(int u) const { return min(max(u - lo, 0), max(hi - lo - 1, 0)); }
-    __device__ __forceinline__ double x(int u) const {
-        const double a = sx[at(u)];
-        return in(u) ? a : gx(*g, u);
-    }
-    __device__ __forceinline__ double y(int u) const {
-        const double a = sy[at(u)];
-        return in(u) ? a : gy(*g, u);
-    }
-    __device__ __forceinline__ long long t(int u) const {
-        const long long a = st[at(u)];
-        return in(u) ? a : g->truth[u];
-    }
-};
-
 template <typename T>
 struct PState {
     T s0, s1, c00, c11, i00, i01, i11;
 };
 
-// parabolic state of the edge from neighbour (xb, yb) in the node's frame
-// (utils.py:273-283); optional full fp64 outputs
 // the Lagrange denominator D = x0 xB (x0 - xB) of the state from neighbour (xb, yb), as
 // pstate forms it in type T
 template <typename T>
@@ -146,28 +104,12 @@ __device__ __forceinline__ T pstate_den(const Frame& f, double xb, double yb) {
     return X0 * XB * (X0 - XB);
 }
 
+// parabolic state from the node-frame abscissae of the old origin (X0) and the neighbour
+// (XB) and the neighbour's ordinate MB, all in type T (utils.py:273-283, closed form above):
+// what every coordinate source shares once its own geometry has produced (X0, XB, MB)
 template <typename T>
-__device__ __forceinline__ PState<T> pstate(const Frame& f, double xb, double yb, bool& singular, double* sv_out,
-                                            double* cov_out, const T* rd_given = nullptr) {
-    const double xB = (xb * f.ca - yb * f.sa) - f.xt;
-    const double mB = (xb * f.sa + yb * f.ca) - f.yt;
-    const double x0 = f.x0;
-    singular = (xB == 0.0) || (xB == x0) || (x0 == 0.0);
-    const double s0d = 4.0 * 4.0, s1d = 0.1 * 0.1;   // sigma0**2, sigmaA**2 = sigmaB**2 (:223-229)
-    if (sv_out || cov_out) {
-        const double rD = 1.0 / (x0 * xB * (x0 - xB));
-        const double r0 = xB * rD, r1 = (x0 - xB) * rD, r2 = -x0 * rD;
-        const double L0[3] = {r0, -xB * r0, 0.0};
-        const double L1[3] = {r1, -(x0 + xB) * r1, 1.0};
-        const double L2[3] = {r2, -x0 * r2, 0.0};
-        if (sv_out) { sv_out[0] = mB * L2[0]; sv_out[1] = mB * L2[1]; sv_out[2] = 0.0; }
-        if (cov_out)
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++)
-                    cov_out[3 * i + j] = s0d * L0[i] * L0[j] + s1d * L1[i] * L1[j] + s1d * L2[i] * L2[j];
-    }
-    const T X0 = (T)x0, XB = (T)xB, MB = (T)mB;
-    const T s0 = (T)s0d, s1 = (T)s1d;
+__device__ __forceinline__ PState<T> pstate_from(T X0, T XB, T MB, const T* rd_given = nullptr) {
+    const T s0 = (T)(4.0 * 4.0), s1 = (T)(0.1 * 0.1);   // sigma0**2, sigmaA**2 = sigmaB**2 (:223-229)
     // the three Lagrange denominators share one reciprocal: D = x0 xB (x0 - xB)
     const T rD = rd_given ? *rd_given : T(1) / (X0 * XB * (X0 - XB));
     const T r0 = XB * rD, r1 = (X0 - XB) * rD, r2 = -X0 * rD;
@@ -187,6 +129,31 @@ __device__ __forceinline__ PState<T> pstate(const Frame& f, double xb, double yb
     return p;
 }
 
+// parabolic state of the edge from neighbour (xb, yb) in the node's frame
+// (utils.py:273-283): fp64 geometry, then the state in type T; optional full fp64 outputs
+template <typename T>
+__device__ __forceinline__ PState<T> pstate(const Frame& f, double xb, double yb, bool& singular, double* sv_out,
+                                            double* cov_out, const T* rd_given = nullptr) {
+    const double xB = (xb * f.ca - yb * f.sa) - f.xt;
+    const double mB = (xb * f.sa + yb * f.ca) - f.yt;
+    const double x0 = f.x0;
+    singular = (xB == 0.0) || (xB == x0) || (x0 == 0.0);
+    const double s0d = 4.0 * 4.0, s1d = 0.1 * 0.1;
+    if (sv_out || cov_out) {
+        const double rD = 1.0 / (x0 * xB * (x0 - xB));
+        const double r0 = xB * rD, r1 = (x0 - xB) * rD, r2 = -x0 * rD;
+        const double L0[3] = {r0, -xB * r0, 0.0};
+        const double L1[3] = {r1, -(x0 + xB) * r1, 1.0};
+        const double L2[3] = {r2, -x0 * r2, 0.0};
+        if (sv_out) { sv_out[0] = mB * L2[0]; sv_out[1] = mB * L2[1]; sv_out[2] = 0.0; }
+        if (cov_out)
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++)
+                    cov_out[3 * i + j] = s0d * L0[i] * L0[j] + s1d * L1[i] * L1[j] + s1d * L2[i] * L2[j];
+    }
+    return pstate_from<T>((T)x0, (T)xB, (T)mB, rd_given);
+}
+
 // KLDistance(mean_i, cov_i, inv_i, mean_j, cov_j, inv_j) (:15-17): the trace of the
 // element-wise product is the sum of the diagonal products
 template <typename T>
@@ -197,11 +164,189 @@ __device__ __forceinline__ T pkl(const PState<T>& a, const PState<T>& b) {
     return tr + (d0 * (d0 * S00 + d1 * S01) + d1 * (d0 * S01 + d1 * S11));
 }
 
-template <typename T, int CAP>
+// the tiled layout's block and LDS window (described at pkl_tile below; the paths size their
+// windows by WWIN)
+constexpr int WBLOCK = 256;
+#ifndef GTF_KL_WWIN
+#define GTF_KL_WWIN 1024
+#endif
+constexpr int WWIN = GTF_KL_WWIN;          // window nodes of the tiled layout (gtf.parabolic.WIN_NODES)
+
+// A path: where a launch's coordinates and truth ids come from and the arithmetic that
+// belongs to them. The kernels below are written once over a path P:
+//   P::In   the kernel argument holding the arrays      P::Out  the output struct
+//   P::XY   a node's coordinates as loaded              P::Tid  a truth id as loaded
+//   P::T    type of states and distances                P::M    type of the stored moments
+//   P::ld / ld_self / ldt / ldt_self   node u's coordinates / truth id (_self: the node's own)
+//   P::frame, P::state, P::grad   node frame, an in-edge's state in it, its gradient dy/dx
+//   P::Win  a tile's window of coordinates and truth ids in LDS (NODE_BYTES each)
+//
+// PathD<T>: gtf_kl_graph's fp64 rows (x, y first of gnn_stride doubles: 4 for x, y, z, r, 2
+// for the compact x, y copy) and int64 truth ids; rotation and translation in fp64, states
+// and distances in T (GTF_F64 / GTF_F32), moments stored in fp64.
+struct XYd {
+    double x, y;
+};
+struct DblIn {   // the fields themselves, not a pointer to the kernel-argument struct
+    const double* gnn;
+    int64_t stride;
+    const int64_t* truth;
+};
+template <typename T_>
+struct PathD {
+    using T = T_;
+    using M = double;
+    using XY = XYd;
+    using Tid = long long;
+    using In = DblIn;
+    using Out = gtf_kl_out;
+    using Fr = Frame;
+    static constexpr bool F64XY = true;   // fp64 coordinates: full fp64 states available (sv / cov)
+    static __device__ __forceinline__ XY ld(const In& c, int u) { return XY{c.gnn[c.stride * u], c.gnn[c.stride * u + 1]}; }
+    static __device__ __forceinline__ XY ld_self(const In& c, int v) {
+        return XY{ld_own(c.gnn + c.stride * v), ld_own(c.gnn + c.stride * v + 1)};
+    }
+    static __device__ __forceinline__ Tid ldt(const In& c, int u) { return c.truth[u]; }
+    static __device__ __forceinline__ Tid ldt_self(const In& c, int v) { return ld_own(c.truth + v); }
+    static __device__ __forceinline__ Fr frame(const In&, const XY& p) { return node_frame_xy(p.x, p.y); }
+    static __device__ __forceinline__ PState<T> state(const Fr& f, const XY& b, bool& singular, double* sv, double* cov,
+                                                      const T* rd = nullptr) {
+        return pstate<T>(f, b.x, b.y, singular, sv, cov, rd);
+    }
+    static __device__ __forceinline__ double grad(const Fr& f, const XY& b) { return (f.y - b.y) / (f.x - b.x); }
+    struct Win {
+        static constexpr int NODE_BYTES = 24;
+        double* sx;
+        double* sy;
+        long long* st;
+        __device__ __forceinline__ explicit Win(char* lds)
+            : sx((double*)lds), sy((double*)lds + WWIN), st((long long*)((double*)lds + 2 * WWIN)) {}
+        __device__ __forceinline__ void put(int i, const XY& p, Tid t) { sx[i] = p.x; sy[i] = p.y; st[i] = t; }
+        __device__ __forceinline__ XY xy(int i) const { return XY{sx[i], sy[i]}; }
+        __device__ __forceinline__ Tid t(int i) const { return st[i]; }
+    };
+};
+
+// PathQ: gtf_kl_q32's fixed-point coordinates -- (qx, qy) int32 pairs, one 8-byte load, times
+// a power-of-two scale s -- and int32 truth ids: 12 bytes per node against 24. Every
+// |q| < 2^30, so a neighbour-minus-node difference is an exact int32 and the translation to
+// the node costs no rounding; the node frame, the rotation of the differences and the state
+// are fp32, the gradient dqy / dqx one fp32 division (summed in fp64 like PathD's, stored
+// as float).
+struct FrameQ {
+    float ca, sa, x0, s;
+    int qx, qy;
+};
+struct Q32In {
+    const int2* xy;
+    const int32_t* truth;
+    float s;
+};
+struct PathQ {
+    using T = float;
+    using M = float;
+    using XY = int2;
+    using Tid = int;
+    using In = Q32In;
+    using Out = gtf_kl_out32;
+    using Fr = FrameQ;
+    static constexpr bool F64XY = false;
+    static __device__ __forceinline__ XY ld(const In& c, int u) { return c.xy[u]; }
+    static __device__ __forceinline__ XY ld_self(const In& c, int v) {
+        if constexpr ((GTF_KL_NT & 4) != 0) {   // (the builtin takes no struct: the pair as one 8-byte word)
+            const long long r = __builtin_nontemporal_load((const long long*)(c.xy + v));
+            return make_int2((int)r, (int)(r >> 32));
+        } else {
+            return c.xy[v];
+        }
+    }
+    static __device__ __forceinline__ Tid ldt(const In& c, int u) { return c.truth[u]; }
+    static __device__ __forceinline__ Tid ldt_self(const In& c, int v) { return ld_own(c.truth + v); }
+    // rotation about the beam line as in node_frame_xy; the node itself lands on (h, 0), so
+    // the old origin's abscissa relative to the node is -h
+    static __device__ __forceinline__ Fr frame(const In& c, const XY& p) {
+        Fr f;
+        f.qx = p.x;
+        f.qy = p.y;
+        f.s = c.s;
+        const float x = (float)p.x * c.s, y = (float)p.y * c.s;
+        const float h = sqrtf(x * x + y * y);
+        f.ca = h > 0.0f ? x / h : 1.0f;
+        f.sa = h > 0.0f ? -y / h : 0.0f;
+        f.x0 = -h;
+        return f;
+    }
+    static __device__ __forceinline__ PState<T> state(const Fr& f, const XY& b, bool& singular, double*, double*,
+                                                      const T* = nullptr) {
+        const float dx = (float)(b.x - f.qx) * f.s, dy = (float)(b.y - f.qy) * f.s;   // (exact int32 differences)
+        const float xB = dx * f.ca - dy * f.sa;
+        const float mB = dx * f.sa + dy * f.ca;
+        singular = (xB == 0.0f) || (xB == f.x0) || (f.x0 == 0.0f);
+        return pstate_from<float>(f.x0, xB, mB);
+    }
+    static __device__ __forceinline__ double grad(const Fr& f, const XY& b) {
+        return (double)((float)(b.y - f.qy) / (float)(b.x - f.qx));
+    }
+    struct Win {
+        static constexpr int NODE_BYTES = 12;
+        int2* sxy;
+        int* st;
+        __device__ __forceinline__ explicit Win(char* lds) : sxy((int2*)lds), st((int*)((int2*)lds + WWIN)) {}
+        __device__ __forceinline__ void put(int i, const XY& p, Tid t) { sxy[i] = p; st[i] = t; }
+        __device__ __forceinline__ XY xy(int i) const { return sxy[i]; }
+        __device__ __forceinline__ Tid t(int i) const { return st[i]; }
+    };
+};
+
+// sv / cov of slot k: the fp64-coordinate paths' STATES instantiations only
+template <bool STATES, typename O>
+__device__ __forceinline__ double* sv_at(const O& o, int64_t k) {
+    if constexpr (STATES) return o.sv + 3 * k;
+    else return nullptr;
+}
+template <bool STATES, typename O>
+__device__ __forceinline__ double* cov_at(const O& o, int64_t k) {
+    if constexpr (STATES) return o.cov + 9 * k;
+    else return nullptr;
+}
+
+// where a kernel reads neighbour coordinates and truth ids: global memory, or a block's
+// LDS window of consecutive nodes [lo, hi) with global memory beyond it
+template <typename P>
+struct GSrc {
+    typename P::In c;
+    __device__ __forceinline__ explicit GSrc(const typename P::In& c_) : c(c_) {}
+    __device__ __forceinline__ bool has_t() const { return c.truth != nullptr; }
+    __device__ __forceinline__ typename P::XY xy(int u) const { return P::ld(c, u); }
+    __device__ __forceinline__ typename P::Tid t(int u) const { return P::ldt(c, u); }
+};
+template <typename P>
+struct WSrc {
+    typename P::In c;
+    typename P::Win w;
+    int lo, hi;
+    __device__ __forceinline__ bool has_t() const { return c.truth != nullptr; }
+    __device__ __forceinline__ bool in(int u) const { return u >= lo && u < hi; }
+    // the LDS read at a clamped index always, the global one only outside the window: a
+    // select of values (a select of an LDS and a global address miscompiles on gfx950)
+    __device__ __forceinline__ int at(int u) const { return min(max(u - lo, 0), max(hi - lo - 1, 0)); }
+    __device__ __forceinline__ typename P::XY xy(int u) const {
+        const typename P::XY a = w.xy(at(u));
+        return in(u) ? a : P::ld(c, u);
+    }
+    __device__ __forceinline__ typename P::Tid t(int u) const {
+        const typename P::Tid a = w.t(at(u));
+        return in(u) ? a : P::ldt(c, u);
+    }
+};
+
+template <typename T, typename Tid, int CAP>
 struct KlStage {
     T s0[CAP], s1[CAP], c00[CAP], c11[CAP], i00[CAP], i01[CAP], i11[CAP];
-    long long tr[CAP];  // neighbour truth ids (pair truth flags without re-gathering)
+    Tid tr[CAP];  // neighbour truth ids (pair truth flags without re-gathering)
 };
+template <typename P, int CAP>
+using Stage = KlStage<typename P::T, typename P::Tid, CAP>;
 
 template <typename T, typename St>
 __device__ __forceinline__ void put(St* s, int i, const PState<T>& p) {
@@ -222,7 +367,16 @@ __device__ __forceinline__ double grp_sum(double x) {
 
 // group sizes of the four degree buckets of gtf_kl_graph.list (d <= 2, <= 4, <= 8, > 8)
 constexpr int BG[4] = {1, 4, 8, 64};
-constexpr size_t stage_bytes(int G, size_t t) { return (size_t)(BLOCK / G) * G * (7 * t + 8); }
+// LDS stage of a BLOCK-thread (sub)block: 7 state numbers of t bytes and a truth id of tid
+// bytes per lane (8 + 8 in PathD<double>, 4 + 8 in PathD<float>, 4 + 4 in PathQ)
+constexpr size_t stage_bytes(int G, size_t t, size_t tid) { return (size_t)(BLOCK / G) * G * (7 * t + tid); }
+constexpr size_t sub_stage_bytes(size_t t, size_t tid) {
+    return stage_bytes(4, t, tid) > stage_bytes(64, t, tid) ? stage_bytes(4, t, tid) : stage_bytes(64, t, tid);
+}
+template <typename P>
+constexpr size_t path_stage_bytes() {
+    return sub_stage_bytes(sizeof(typename P::T), sizeof(typename P::Tid));
+}
 
 // one node per group of G lanes; states staged in LDS when d <= G (always, except in
 // the wavefront bucket beyond 64 in-edges, where pair lanes recompute both states)
@@ -241,12 +395,15 @@ __device__ __forceinline__ void pair_table_fill(uint16_t* tab) {
     else __syncthreads();
 }
 
-template <typename T, int G, bool STATES, typename S>
-__device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_kl_out& o, const S& src, int v, int lo,
-                                              int d, int64_t base, int gl, KlStage<T, G>* stg,
+template <typename P, int G, bool STATES, typename S>
+__device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const typename P::Out& o, const S& src, int v,
+                                              int lo, int d, int64_t base, int gl, Stage<P, G>* stg,
                                               const uint16_t* ptab = nullptr) {
+    using T = typename P::T;
+    using M = typename P::M;
+    using Tid = typename P::Tid;
     if (d < 1) return;
-    const Frame f = node_frame_xy(src.x(v), src.y(v));
+    const typename P::Fr f = P::frame(src.c, src.xy(v));
 
     // states of the node's in-edges and the gradients dy/dx (utils.py:249-254, 273-283)
     double gsum = 0.0, gr0 = 0.0;
@@ -254,16 +411,15 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
     for (int q = gl; q < d; q += G) {
         const int k = lo + q;
         const int u = g.slot_src[k];
-        const double xb = src.x(u), yb = src.y(u);
+        const typename P::XY cb = src.xy(u);
         bool s;
-        const PState<T> p = pstate<T>(f, xb, yb, s, STATES ? o.sv + 3 * (int64_t)k : nullptr,
-                                      STATES ? o.cov + 9 * (int64_t)k : nullptr);
+        const PState<T> p = P::state(f, cb, s, sv_at<STATES>(o, k), cov_at<STATES>(o, k));
         sing |= s;
         if (d <= G) {
             put<T>(stg, q, p);
-            if (g.truth) stg->tr[q] = src.t(u);
+            if (src.has_t()) stg->tr[q] = src.t(u);
         }
-        const double gr = (f.y - yb) / (f.x - xb);
+        const double gr = P::grad(f, cb);
         if (q == gl) gr0 = gr;
         gsum += gr;
     }
@@ -275,14 +431,14 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
             double gr = gr0;
             if (q != gl) {
                 const int u = g.slot_src[lo + q];
-                gr = (f.y - src.y(u)) / (f.x - src.x(u));
+                gr = P::grad(f, src.xy(u));
             }
             vs += (gr - mean) * (gr - mean);
         }
         vs = grp_sum<G>(vs);
         if (gl == 0) {
-            if (o.emp_var) st_out(o.emp_var + (v), (double)(vs / (double)d));
-            if (o.emp_mean) st_out(o.emp_mean + (v), (double)(mean));
+            if (o.emp_var) st_out(o.emp_var + (v), (M)(vs / (double)d));
+            if (o.emp_mean) st_out(o.emp_mean + (v), (M)(mean));
         }
     }
     gtf::wave_lds_sync();
@@ -290,7 +446,7 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
     // pairs i > j, row-major, round-robin over the lanes: consecutive lanes write
     // consecutive distances (calc_pairwise_distances, :19-25)
     const int np = d * (d - 1) / 2;
-    const long long tv = g.truth ? src.t(v) : 0;
+    const Tid tv = src.has_t() ? src.t(v) : 0;
     T* kl = (T*)o.kl;
     for (int t = gl; t < np; t += G) {
         int i, j;
@@ -302,7 +458,7 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
             gtf::pair_ij(t, i, j);
         }
         PState<T> a, b;
-        long long ti = 0, tj = 0;
+        Tid ti = 0, tj = 0;
         if (d <= G) {
             a = get<T>(stg, i);
             b = get<T>(stg, j);
@@ -310,8 +466,8 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
         } else {  // beyond the LDS stage (wavefront bucket, d > 64): recompute both states
             bool s;
             const int ui = g.slot_src[lo + i], uj = g.slot_src[lo + j];
-            a = pstate<T>(f, src.x(ui), src.y(ui), s, nullptr, nullptr);
-            b = pstate<T>(f, src.x(uj), src.y(uj), s, nullptr, nullptr);
+            a = P::state(f, src.xy(ui), s, nullptr, nullptr);
+            b = P::state(f, src.xy(uj), s, nullptr, nullptr);
             if (o.truth) { ti = src.t(ui); tj = src.t(uj); }
         }
         st_out(kl + (base + t), (T)(pkl<T>(a, b)));
@@ -319,23 +475,23 @@ __device__ __forceinline__ void pkl_node_core(const gtf_kl_graph& g, const gtf_k
     }
 }
 
-template <typename T, int G, bool STATES, typename S>
-__device__ __forceinline__ void pkl_node_body(const gtf_kl_graph& g, const gtf_kl_out& o, const S& src, int v, int gl,
-                                              KlStage<T, G>* stg, const uint16_t* ptab = nullptr) {
+template <typename P, int G, bool STATES, typename S>
+__device__ __forceinline__ void pkl_node_body(const gtf_kl_graph& g, const typename P::Out& o, const S& src, int v,
+                                              int gl, Stage<P, G>* stg, const uint16_t* ptab = nullptr) {
     const int lo = g.slot_ptr[v], d = g.slot_ptr[v + 1] - lo;
     if (d < 1) return;
-    pkl_node_core<T, G, STATES>(g, o, src, v, lo, d, g.pair_ptr[v], gl, stg, ptab);
+    pkl_node_core<P, G, STATES>(g, o, src, v, lo, d, g.pair_ptr[v], gl, stg, ptab);
 }
 
-template <typename T, int G, bool STATES>
-__device__ __forceinline__ void pkl_node(const gtf_kl_graph& g, const gtf_kl_out& o, const int32_t* list, int count,
-                                         int bid, char* smem, int first = 0, int tid = -1,
-                                         const uint16_t* ptab = nullptr) {
+template <typename P, int G, bool STATES>
+__device__ __forceinline__ void pkl_node(const gtf_kl_graph& g, const typename P::In& c, const typename P::Out& o,
+                                         const int32_t* list, int count, int bid, char* smem, int first = 0,
+                                         int tid = -1, const uint16_t* ptab = nullptr) {
     if (tid < 0) tid = (int)threadIdx.x;   // (tid: the thread in a BLOCK-thread (sub)block)
     const int gi = (bid * BLOCK + tid) / G;
     if (gi >= count) return;  // group-uniform
     const int v = list ? list[gi] : first + gi;   // (ordered layout: the bucket is a node range)
-    pkl_node_body<T, G, STATES>(g, o, GSrc(g), v, tid & (G - 1), (KlStage<T, G>*)smem + tid / G, ptab);
+    pkl_node_body<P, G, STATES>(g, o, GSrc<P>(c), v, tid & (G - 1), (Stage<P, G>*)smem + tid / G, ptab);
 }
 
 // d <= 2: one thread per node, both states in registers (the bulk of a TrackML
@@ -354,12 +510,13 @@ constexpr int NPT = GTF_KL_NPT;
 #define GTF_KL_NPT_ORD 1
 #endif
 constexpr int NPT_ORD = GTF_KL_NPT_ORD;
+template <typename P>
 struct B0Node {
     int v, u0, u1;
     bool ok, two;
     int64_t l, pp;
-    double xv, yv, x0, y0, x1, y1;
-    long long tv, t0, t1;
+    typename P::XY cv, c0, c1;
+    typename P::Tid tv, t0, t1;
 };
 
 // GTF_KL_RCP (fp64): the node's two Lagrange denominators and two gradient run lengths share
@@ -371,20 +528,22 @@ struct B0Node {
 #ifndef GTF_KL_RCP
 #define GTF_KL_RCP 0
 #endif
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_b0_finish(const gtf_kl_out& o, const B0Node& n) {
-    const Frame f = node_frame_xy(n.xv, n.yv);
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_b0_finish(const typename P::In& c, const typename P::Out& o, const B0Node<P>& n) {
+    using T = typename P::T;
+    using M = typename P::M;
+    const typename P::Fr f = P::frame(c, n.cv);
     bool s0, s1 = false;
-    const double e0 = f.x - n.x0, e1 = n.two ? f.x - n.x1 : 1.0;
     double re0 = 0.0, re1 = 0.0;
     T rda = T(0), rdb = T(0);
     bool shared = false;
-    if constexpr (GTF_KL_RCP && sizeof(T) == 8 && !STATES) {
-        const double da = pstate_den<double>(f, n.x0, n.y0), db = n.two ? pstate_den<double>(f, n.x1, n.y1) : 1.0;
-        const double p1 = da * db, p2 = p1 * e0, P = p2 * e1;
-        shared = fabs(P) >= 2.2250738585072014e-308 && fabs(P) <= 1.7976931348623157e308;
+    if constexpr (GTF_KL_RCP && P::F64XY && sizeof(T) == 8 && !STATES) {
+        const double e0 = f.x - n.c0.x, e1 = n.two ? f.x - n.c1.x : 1.0;
+        const double da = pstate_den<double>(f, n.c0.x, n.c0.y), db = n.two ? pstate_den<double>(f, n.c1.x, n.c1.y) : 1.0;
+        const double p1 = da * db, p2 = p1 * e0, Pr = p2 * e1;
+        shared = fabs(Pr) >= 2.2250738585072014e-308 && fabs(Pr) <= 1.7976931348623157e308;
         if (shared) {
-            const double R = 1.0 / P;
+            const double R = 1.0 / Pr;
             re1 = R * p2;
             const double t1 = R * e1;
             re0 = t1 * p1;
@@ -393,31 +552,36 @@ __device__ __forceinline__ void pkl_b0_finish(const gtf_kl_out& o, const B0Node&
             rda = t2 * db;
         }
     }
-    const PState<T> a = pstate<T>(f, n.x0, n.y0, s0, STATES ? o.sv + 3 * n.l : nullptr, STATES ? o.cov + 9 * n.l : nullptr,
-                                  shared ? &rda : nullptr);
+    const PState<T> a = P::state(f, n.c0, s0, sv_at<STATES>(o, n.l), cov_at<STATES>(o, n.l), shared ? &rda : nullptr);
     PState<T> b = a;
     if (n.two)
-        b = pstate<T>(f, n.x1, n.y1, s1, STATES ? o.sv + 3 * (n.l + 1) : nullptr, STATES ? o.cov + 9 * (n.l + 1) : nullptr,
-                      shared ? &rdb : nullptr);
+        b = P::state(f, n.c1, s1, sv_at<STATES>(o, n.l + 1), cov_at<STATES>(o, n.l + 1), shared ? &rdb : nullptr);
     if ((s0 || s1) && o.err) atomicOr(o.err, (uint32_t)GTF_ERR_SINGULAR_H);
-    const double g0 = shared ? (f.y - n.y0) * re0 : (f.y - n.y0) / e0;
-    const double g1 = n.two ? (shared ? (f.y - n.y1) * re1 : (f.y - n.y1) / e1) : g0;
+    double g0, g1;
+    if constexpr (GTF_KL_RCP && P::F64XY && sizeof(T) == 8 && !STATES) {
+        g0 = shared ? (f.y - n.c0.y) * re0 : P::grad(f, n.c0);
+        g1 = n.two ? (shared ? (f.y - n.c1.y) * re1 : P::grad(f, n.c1)) : g0;
+    } else {
+        g0 = P::grad(f, n.c0);
+        g1 = n.two ? P::grad(f, n.c1) : g0;
+    }
     // / 2 and / 1 as exact scalings
     const double mean = n.two ? (g0 + g1) * 0.5 : g0;
     if (o.emp_var)
-        st_out(o.emp_var + (n.v), (double)(n.two ? ((g0 - mean) * (g0 - mean) + (g1 - mean) * (g1 - mean)) * 0.5
-                                                 : 0.0 * (g0 - mean)));
-    if (o.emp_mean) st_out(o.emp_mean + (n.v), (double)(mean));
+        st_out(o.emp_var + (n.v), (M)(n.two ? ((g0 - mean) * (g0 - mean) + (g1 - mean) * (g1 - mean)) * 0.5
+                                            : 0.0 * (g0 - mean)));
+    if (o.emp_mean) st_out(o.emp_mean + (n.v), (M)(mean));
     if (n.two) {
         st_out((T*)o.kl + (n.pp), (T)(pkl<T>(b, a)));   // pair (i, j) = (1, 0)
         if (o.truth) st_out(o.truth + (n.pp), (int8_t)(n.tv == n.t1 && n.t1 == n.t0 && n.tv == n.t0));
     }
 }
 
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node1_ordered(const gtf_kl_graph& g, const gtf_kl_out& o, int bid) {
-    B0Node n[NPT_ORD];
-    const bool tr = o.truth && g.truth;
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node1_ordered(const gtf_kl_graph& g, const typename P::In& c,
+                                                  const typename P::Out& o, int bid) {
+    B0Node<P> n[NPT_ORD];
+    const bool tr = o.truth && c.truth;
 #pragma unroll
     for (int j = 0; j < NPT_ORD; j++) {   // round 1: own fields and sender lists
         const int gi = (bid * NPT_ORD + j) * BLOCK + (int)threadIdx.x;
@@ -427,9 +591,8 @@ __device__ __forceinline__ void pkl_node1_ordered(const gtf_kl_graph& g, const g
         n[j].two = gi >= g.n_d1;
         n[j].l = g.slot0 + (n[j].two ? g.n_d1 + 2 * (int64_t)(gi - g.n_d1) : gi);
         n[j].pp = g.pair0 + (gi - g.n_d1);
-        n[j].xv = ld_own(g.gnn + gnn_row(g, n[j].v));
-        n[j].yv = ld_own(g.gnn + gnn_row(g, n[j].v) + 1);
-        n[j].tv = tr ? ld_own(g.truth + n[j].v) : 0;
+        n[j].cv = P::ld_self(c, n[j].v);
+        n[j].tv = tr ? P::ldt_self(c, n[j].v) : 0;
         n[j].u0 = ld_list(g.slot_src + n[j].l);
         n[j].u1 = n[j].two ? ld_list(g.slot_src + n[j].l + 1) : n[j].u0;
     }
@@ -441,17 +604,15 @@ __device__ __forceinline__ void pkl_node1_ordered(const gtf_kl_graph& g, const g
 #else
         const int w0 = n[j].u0, w1 = n[j].u1;
 #endif
-        n[j].x0 = gx(g, w0);
-        n[j].y0 = gy(g, w0);
-        n[j].x1 = gx(g, w1);
-        n[j].y1 = gy(g, w1);
-        n[j].t0 = tr ? g.truth[w0] : 0;
-        n[j].t1 = tr ? g.truth[w1] : 0;
+        n[j].c0 = P::ld(c, w0);
+        n[j].c1 = P::ld(c, w1);
+        n[j].t0 = tr ? P::ldt(c, w0) : 0;
+        n[j].t1 = tr ? P::ldt(c, w1) : 0;
     }
 #pragma unroll
     for (int j = 0; j < NPT_ORD; j++)
         if (n[j].ok) {
-            pkl_b0_finish<T, STATES>(o, n[j]);
+            pkl_b0_finish<P, STATES>(c, o, n[j]);
 #ifdef GTF_KL_DIAG_NODEP
             asm volatile("" ::"v"(n[j].u0), "v"(n[j].u1));   // (the sender-list loads stay)
 #endif
@@ -460,29 +621,30 @@ __device__ __forceinline__ void pkl_node1_ordered(const gtf_kl_graph& g, const g
 
 // one- or two-edge node v (two: its slots l, l + 1 with senders u0, u1 and pair pp; else
 // slot l, sender u0): both states in registers
-template <typename T, bool STATES, typename S>
-__device__ __forceinline__ void pkl_b0_body(const gtf_kl_graph& g, const gtf_kl_out& o, const S& src, int v, bool two,
-                                            int64_t l, int64_t pp, int u0, int u1) {
-    const bool tr = o.truth && g.truth;
-    B0Node n;
+template <typename P, bool STATES, typename S>
+__device__ __forceinline__ void pkl_b0_body(const typename P::Out& o, const S& src, int v, bool two, int64_t l,
+                                            int64_t pp, int u0, int u1) {
+    const bool tr = o.truth && src.has_t();
+    B0Node<P> n;
     n.ok = true;
     n.v = v, n.two = two, n.l = l, n.pp = pp, n.u0 = u0, n.u1 = u1;
-    n.xv = src.x(v), n.yv = src.y(v);
+    n.cv = src.xy(v);
     n.tv = tr ? src.t(v) : 0;
-    n.x0 = src.x(u0), n.y0 = src.y(u0);
-    n.x1 = src.x(u1), n.y1 = src.y(u1);
+    n.c0 = src.xy(u0);
+    n.c1 = src.xy(u1);
     n.t0 = tr ? src.t(u0) : 0;
     n.t1 = tr ? src.t(u1) : 0;
-    pkl_b0_finish<T, STATES>(o, n);
+    pkl_b0_finish<P, STATES>(src.c, o, n);
 }
 
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node1(const gtf_kl_graph& g, const gtf_kl_out& o, const int32_t* list, int count,
-                                          int bid) {
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node1(const gtf_kl_graph& g, const typename P::In& c, const typename P::Out& o,
+                                          const int32_t* list, int count, int bid) {
     int v[NPT], lo[NPT], d[NPT], u0[NPT], u1[NPT];
-    double xv[NPT], yv[NPT], x0[NPT], y0[NPT], x1[NPT], y1[NPT];
+    typename P::XY cv[NPT], c0[NPT], c1[NPT];
     int64_t pp[NPT];
-    long long tv[NPT], t0[NPT], t1[NPT];
+    typename P::Tid tv[NPT], t0[NPT], t1[NPT];
+    const bool tr = o.truth && c.truth;
 #pragma unroll
     for (int j = 0; j < NPT; j++) {
         const int gi = (bid * NPT + j) * BLOCK + (int)threadIdx.x;
@@ -494,10 +656,9 @@ __device__ __forceinline__ void pkl_node1(const gtf_kl_graph& g, const gtf_kl_ou
         if (v[j] >= 0) {
             lo[j] = g.slot_ptr[v[j]];
             d[j] = g.slot_ptr[v[j] + 1] - lo[j];
-            xv[j] = gx(g, v[j]);
-            yv[j] = gy(g, v[j]);
+            cv[j] = P::ld(c, v[j]);
             pp[j] = g.pair_ptr[v[j]];
-            tv[j] = (o.truth && g.truth) ? g.truth[v[j]] : 0;
+            tv[j] = tr ? P::ldt(c, v[j]) : 0;
         }
         if (d[j] < 1 || d[j] > 2) d[j] = 0;
     }
@@ -510,26 +671,24 @@ __device__ __forceinline__ void pkl_node1(const gtf_kl_graph& g, const gtf_kl_ou
 #pragma unroll
     for (int j = 0; j < NPT; j++)
         if (d[j]) {
-            x0[j] = gx(g, u0[j]);
-            y0[j] = gy(g, u0[j]);
-            x1[j] = gx(g, u1[j]);
-            y1[j] = gy(g, u1[j]);
-            if (o.truth && g.truth) {
-                t0[j] = g.truth[u0[j]];
-                t1[j] = g.truth[u1[j]];
+            c0[j] = P::ld(c, u0[j]);
+            c1[j] = P::ld(c, u1[j]);
+            if (tr) {
+                t0[j] = P::ldt(c, u0[j]);
+                t1[j] = P::ldt(c, u1[j]);
             }
         }
 #pragma unroll
     for (int j = 0; j < NPT; j++) {   // (the ordered and tiled layouts' bucket-0 arithmetic, bit for bit)
         if (!d[j]) continue;
-        B0Node n;
+        B0Node<P> n;
         n.ok = true;
         n.v = v[j], n.two = d[j] == 2, n.l = lo[j], n.pp = pp[j], n.u0 = u0[j], n.u1 = u1[j];
-        n.xv = xv[j], n.yv = yv[j], n.x0 = x0[j], n.y0 = y0[j], n.x1 = x1[j], n.y1 = y1[j];
+        n.cv = cv[j], n.c0 = c0[j], n.c1 = c1[j];
         n.tv = tv[j];
-        n.t0 = (o.truth && g.truth) ? t0[j] : 0;
-        n.t1 = (o.truth && g.truth) ? t1[j] : 0;
-        pkl_b0_finish<T, STATES>(o, n);
+        n.t0 = tr ? t0[j] : 0;
+        n.t1 = tr ? t1[j] : 0;
+        pkl_b0_finish<P, STATES>(c, o, n);
     }
 }
 
@@ -541,20 +700,23 @@ __device__ __forceinline__ void pkl_node1(const gtf_kl_graph& g, const gtf_kl_ou
 #define GTF_KL_B1_LANES 0
 #endif
 // node v with d in 1..4 in-edges from slot lo (senders u[0..d)) and pairs from base
-template <typename T, bool STATES, typename S>
-__device__ __forceinline__ void pkl_node4_core(const gtf_kl_graph& g, const gtf_kl_out& o, const S& src, int v, int lo,
-                                               int d, int64_t base, const int (&u)[4]) {
-    const double xv = src.x(v), yv = src.y(v);
-    const long long tv = (o.truth && g.truth) ? src.t(v) : 0;
-    double xb[4], yb[4];
-    long long tu[4];
+template <typename P, bool STATES, typename S>
+__device__ __forceinline__ void pkl_node4_core(const typename P::Out& o, const S& src, int v, int lo, int d,
+                                               int64_t base, const int (&u)[4]) {
+    using T = typename P::T;
+    using M = typename P::M;
+    using Tid = typename P::Tid;
+    const bool tr = o.truth && src.has_t();
+    const typename P::XY cv = src.xy(v);
+    const Tid tv = tr ? src.t(v) : 0;
+    typename P::XY cb[4];
+    Tid tu[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        xb[q] = q < d ? src.x(u[q]) : 0.0;
-        yb[q] = q < d ? src.y(u[q]) : 0.0;
-        tu[q] = (q < d && o.truth && g.truth) ? src.t(u[q]) : 0;
+        cb[q] = q < d ? src.xy(u[q]) : typename P::XY{};
+        tu[q] = (q < d && tr) ? src.t(u[q]) : 0;
     }
-    const Frame f = node_frame_xy(xv, yv);
+    const typename P::Fr f = P::frame(src.c, cv);
     PState<T> st[4];
     double gr[4];
     bool sing = false;
@@ -562,10 +724,9 @@ __device__ __forceinline__ void pkl_node4_core(const gtf_kl_graph& g, const gtf_
     for (int q = 0; q < 4; q++) {
         if (q < d) {
             bool s;
-            st[q] = pstate<T>(f, xb[q], yb[q], s, STATES ? o.sv + 3 * (int64_t)(lo + q) : nullptr,
-                              STATES ? o.cov + 9 * (int64_t)(lo + q) : nullptr);
+            st[q] = P::state(f, cb[q], s, sv_at<STATES>(o, lo + q), cov_at<STATES>(o, lo + q));
             sing |= s;
-            gr[q] = (f.y - yb[q]) / (f.x - xb[q]);
+            gr[q] = P::grad(f, cb[q]);
         }
     }
     if (sing && o.err) atomicOr(o.err, (uint32_t)GTF_ERR_SINGULAR_H);
@@ -579,8 +740,8 @@ __device__ __forceinline__ void pkl_node4_core(const gtf_kl_graph& g, const gtf_
 #pragma unroll
         for (int q = 1; q < 4; q++)
             if (q < d) vs = vs + (gr[q] - mean) * (gr[q] - mean);
-        if (o.emp_var) st_out(o.emp_var + (v), (double)(vs / (double)d));
-        if (o.emp_mean) st_out(o.emp_mean + (v), (double)(mean));
+        if (o.emp_var) st_out(o.emp_var + (v), (M)(vs / (double)d));
+        if (o.emp_mean) st_out(o.emp_mean + (v), (M)(mean));
     }
     T* kl = (T*)o.kl;
     int t = 0;
@@ -595,24 +756,24 @@ __device__ __forceinline__ void pkl_node4_core(const gtf_kl_graph& g, const gtf_
             }
 }
 
-template <typename T, bool STATES, typename S>
-__device__ __forceinline__ void pkl_node4_body(const gtf_kl_graph& g, const gtf_kl_out& o, const S& src, int v) {
+template <typename P, bool STATES, typename S>
+__device__ __forceinline__ void pkl_node4_body(const gtf_kl_graph& g, const typename P::Out& o, const S& src, int v) {
     const int lo = g.slot_ptr[v], d = g.slot_ptr[v + 1] - lo;
     const int64_t base = g.pair_ptr[v];
     if (d < 1 || d > 4) return;
     int u[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) u[q] = q < d ? g.slot_src[lo + q] : 0;
-    pkl_node4_core<T, STATES>(g, o, src, v, lo, d, base, u);
+    pkl_node4_core<P, STATES>(o, src, v, lo, d, base, u);
 }
 
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node4(const gtf_kl_graph& g, const gtf_kl_out& o, const int32_t* list, int count,
-                                          int bid, int first, int tid = -1) {
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node4(const gtf_kl_graph& g, const typename P::In& c, const typename P::Out& o,
+                                          const int32_t* list, int count, int bid, int first, int tid = -1) {
     if (tid < 0) tid = (int)threadIdx.x;
     const int gi = bid * BLOCK + tid;
     if (gi >= count) return;
-    pkl_node4_body<T, STATES>(g, o, GSrc(g), list ? list[gi] : first + gi);
+    pkl_node4_body<P, STATES>(g, o, GSrc<P>(c), list ? list[gi] : first + gi);
 }
 
 struct KlBuckets {
@@ -628,8 +789,9 @@ struct KlBuckets {
 // ordered layout with degree runs: bucket-1 entry gi (three- then four-edge nodes), its
 // slots, senders and pairs by arithmetic -- the node's own fields and its sender list are
 // one round of independent loads, the senders' coordinates the second
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node4_runs(const gtf_kl_graph& g, const gtf_kl_out& o, const KlBuckets& bk, int bid) {
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node4_runs(const gtf_kl_graph& g, const typename P::In& c,
+                                               const typename P::Out& o, const KlBuckets& bk, int bid) {
     const int gi = bid * BLOCK + (int)threadIdx.x;
     if (gi >= g.count[1]) return;
     const bool three = gi < bk.n3;
@@ -639,35 +801,36 @@ __device__ __forceinline__ void pkl_node4_runs(const gtf_kl_graph& g, const gtf_
     int u[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) u[q] = q < d ? ld_list(g.slot_src + lo + q) : 0;
-    pkl_node4_core<T, STATES>(g, o, GSrc(g), g.first[1] + gi, (int)lo, d, pp, u);
+    pkl_node4_core<P, STATES>(o, GSrc<P>(c), g.first[1] + gi, (int)lo, d, pp, u);
 }
 
 // ... bucket-1 entry gi on a 4-lane group (GTF_KL_B1_LANES: the LDS-staged form, fewer
 // registers than the thread-per-node one)
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node4l_runs(const gtf_kl_graph& g, const gtf_kl_out& o, const KlBuckets& bk, int bid,
-                                                char* smem) {
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node4l_runs(const gtf_kl_graph& g, const typename P::In& c,
+                                                const typename P::Out& o, const KlBuckets& bk, int bid, char* smem) {
     const int gi = (bid * BLOCK + (int)threadIdx.x) / 4;
     if (gi >= g.count[1]) return;   // group-uniform
     const bool three = gi < bk.n3;
     const int d = three ? 3 : 4;
     const int64_t lo = bk.slot1 + (three ? 3 * (int64_t)gi : 3 * (int64_t)bk.n3 + 4 * (int64_t)(gi - bk.n3));
     const int64_t pp = bk.pair1 + (three ? 3 * (int64_t)gi : 3 * (int64_t)bk.n3 + 6 * (int64_t)(gi - bk.n3));
-    pkl_node_core<T, 4, STATES>(g, o, GSrc(g), g.first[1] + gi, (int)lo, d, pp, (int)threadIdx.x & 3,
-                                (KlStage<T, 4>*)smem + (int)threadIdx.x / 4);
+    pkl_node_core<P, 4, STATES>(g, o, GSrc<P>(c), g.first[1] + gi, (int)lo, d, pp, (int)threadIdx.x & 3,
+                                (Stage<P, 4>*)smem + (int)threadIdx.x / 4);
 }
 
 // ... and bucket-2 group gi (runs of 5, 6, 7, 8 in-edges) on G = 8 lanes
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_node8_runs(const gtf_kl_graph& g, const gtf_kl_out& o, const KlBuckets& bk, int bid,
-                                               char* smem, const uint16_t* ptab = nullptr) {
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_node8_runs(const gtf_kl_graph& g, const typename P::In& c,
+                                               const typename P::Out& o, const KlBuckets& bk, int bid, char* smem,
+                                               const uint16_t* ptab = nullptr) {
     const int gi = (bid * BLOCK + (int)threadIdx.x) / 8;
     if (gi >= g.count[2]) return;   // group-uniform
     const int k = gi >= bk.r2[3] ? 3 : gi >= bk.r2[2] ? 2 : gi >= bk.r2[1] ? 1 : 0;
     const int d = 5 + k, i = gi - bk.r2[k];
-    pkl_node_core<T, 8, STATES>(g, o, GSrc(g), g.first[2] + gi, (int)(bk.slot2[k] + (int64_t)i * d), d,
+    pkl_node_core<P, 8, STATES>(g, o, GSrc<P>(c), g.first[2] + gi, (int)(bk.slot2[k] + (int64_t)i * d), d,
                                 bk.pair2[k] + (int64_t)i * (d * (d - 1) / 2), (int)threadIdx.x & 7,
-                                (KlStage<T, 8>*)smem + (int)threadIdx.x / 8, ptab);
+                                (Stage<P, 8>*)smem + (int)threadIdx.x / 8, ptab);
 }
 
 // one launch over the four buckets; wavefront-bucket blocks first (longest-running)
@@ -679,11 +842,10 @@ __device__ __forceinline__ void pkl_node8_runs(const gtf_kl_graph& g, const gtf_
 #define GTF_KL_WAVES 5
 #endif
 #define KL_ATTR __attribute__((amdgpu_waves_per_eu(GTF_KL_WAVES)))
-template <typename T, bool STATES>
-__global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, gtf_kl_out o, KlBuckets bk) {
-    __shared__ __attribute__((aligned(16))) char smem[stage_bytes(4, sizeof(T)) > stage_bytes(64, sizeof(T))
-                                                          ? stage_bytes(4, sizeof(T))
-                                                          : stage_bytes(64, sizeof(T))];
+template <typename P, bool STATES>
+__global__ void __launch_bounds__(BLOCK) KL_ATTR
+k_parabolic_kl(gtf_kl_graph g, typename P::In c, typename P::Out o, KlBuckets bk) {
+    __shared__ __attribute__((aligned(16))) char smem[path_stage_bytes<P>()];
     // bucket block ranges are multiples of 8, each remapped XCD-contiguous on its own:
     // neighbouring nodes (one event's hits) share an L2. GTF_KL_ORDER: 0 the
     // > 8, 5..8, 3..4-edge buckets' blocks first, then bucket 0; 1 bucket 0 first; 2 the
@@ -697,7 +859,7 @@ __global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, 
 #endif
     if (GTF_KL_ORDER == 1 && bk.ordered) {
         if (b < bk.blocks[0]) {
-            pkl_node1_ordered<T, STATES>(g, o, gtf::xcd_local(b, bk.blocks[0]));
+            pkl_node1_ordered<P, STATES>(g, c, o, gtf::xcd_local(b, bk.blocks[0]));
             return;
         }
         b -= bk.blocks[0];
@@ -706,7 +868,7 @@ __global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, 
         const int64_t tot = rest + bk.blocks[0];
         const int upto = (int)(((int64_t)b + 1) * rest / tot);   // other-bucket blocks among [0, b]
         if (upto == (int)((int64_t)b * rest / tot)) {           // b is a bucket-0 block
-            pkl_node1_ordered<T, STATES>(g, o, b - upto);
+            pkl_node1_ordered<P, STATES>(g, c, o, b - upto);
             return;
         }
         b = upto - 1;
@@ -718,7 +880,7 @@ __global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, 
         const int ch = b / 8, x = b % 8;
         const int upto = ch >= tot ? (int)rest : (int)(((int64_t)ch + 1) * rest / tot);
         if (ch >= tot || upto == (int)((int64_t)ch * rest / tot)) {
-            pkl_node1_ordered<T, STATES>(g, o, gtf::xcd_local((ch - upto) * 8 + x, bk.blocks[0]));
+            pkl_node1_ordered<P, STATES>(g, c, o, gtf::xcd_local((ch - upto) * 8 + x, bk.blocks[0]));
             return;
         }
         b = (upto - 1) * 8 + x;
@@ -726,30 +888,30 @@ __global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, 
     __shared__ uint16_t s_pair[PTAB];   // (filled by the lane-group buckets' blocks only)
     if (b < bk.blocks[3]) {
         pair_table_fill(s_pair);
-        pkl_node<T, 64, STATES>(g, o, g.list[3], g.count[3], gtf::xcd_local(b, bk.blocks[3]), smem, g.first[3], -1,
+        pkl_node<P, 64, STATES>(g, c, o, g.list[3], g.count[3], gtf::xcd_local(b, bk.blocks[3]), smem, g.first[3], -1,
                                 s_pair);
         return;
     }
     b -= bk.blocks[3];
     if (b < bk.blocks[2]) {
         pair_table_fill(s_pair);
-        if (bk.runs) pkl_node8_runs<T, STATES>(g, o, bk, gtf::xcd_local(b, bk.blocks[2]), smem, s_pair);
-        else pkl_node<T, 8, STATES>(g, o, g.list[2], g.count[2], gtf::xcd_local(b, bk.blocks[2]), smem, g.first[2],
+        if (bk.runs) pkl_node8_runs<P, STATES>(g, c, o, bk, gtf::xcd_local(b, bk.blocks[2]), smem, s_pair);
+        else pkl_node<P, 8, STATES>(g, c, o, g.list[2], g.count[2], gtf::xcd_local(b, bk.blocks[2]), smem, g.first[2],
                                     -1, s_pair);
         return;
     }
     b -= bk.blocks[2];
     if (b < bk.blocks[1]) {
-        if (GTF_KL_B1_LANES && bk.runs) pkl_node4l_runs<T, STATES>(g, o, bk, gtf::xcd_local(b, bk.blocks[1]), smem);
-        else if (GTF_KL_B1_LANES) pkl_node<T, 4, STATES>(g, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]), smem, g.first[1]);
-        else if (bk.runs) pkl_node4_runs<T, STATES>(g, o, bk, gtf::xcd_local(b, bk.blocks[1]));
-        else pkl_node4<T, STATES>(g, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]), g.first[1]);
+        if (GTF_KL_B1_LANES && bk.runs) pkl_node4l_runs<P, STATES>(g, c, o, bk, gtf::xcd_local(b, bk.blocks[1]), smem);
+        else if (GTF_KL_B1_LANES) pkl_node<P, 4, STATES>(g, c, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]), smem, g.first[1]);
+        else if (bk.runs) pkl_node4_runs<P, STATES>(g, c, o, bk, gtf::xcd_local(b, bk.blocks[1]));
+        else pkl_node4<P, STATES>(g, c, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]), g.first[1]);
         return;
     }
     b -= bk.blocks[1];
     if (GTF_KL_ORDER != 0 && bk.ordered) return;   // (bucket 0 taken above)
-    if (bk.ordered) pkl_node1_ordered<T, STATES>(g, o, gtf::xcd_local(b, bk.blocks[0]));
-    else pkl_node1<T, STATES>(g, o, g.list[0], g.count[0], gtf::xcd_local(b, bk.blocks[0]));
+    if (bk.ordered) pkl_node1_ordered<P, STATES>(g, c, o, gtf::xcd_local(b, bk.blocks[0]));
+    else pkl_node1<P, STATES>(g, c, o, g.list[0], g.count[0], gtf::xcd_local(b, bk.blocks[0]));
 }
 
 // GTF_KL_SPLIT_B0 (ordered layout): the one-/two-edge bucket in a launch of its own at
@@ -762,10 +924,10 @@ __global__ void __launch_bounds__(BLOCK) KL_ATTR k_parabolic_kl(gtf_kl_graph g, 
 #ifndef GTF_KL_B0_WAVES
 #define GTF_KL_B0_WAVES 8
 #endif
-template <typename T, bool STATES>
+template <typename P, bool STATES>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GTF_KL_B0_WAVES)))
-k_parabolic_kl_b0(gtf_kl_graph g, gtf_kl_out o, int nblk) {
-    pkl_node1_ordered<T, STATES>(g, o, gtf::xcd_local(blockIdx.x, nblk));
+k_parabolic_kl_b0(gtf_kl_graph g, typename P::In c, typename P::Out o, int nblk) {
+    pkl_node1_ordered<P, STATES>(g, c, o, gtf::xcd_local(blockIdx.x, nblk));
 }
 
 // Tiled layout (gtf_kl_graph.blk, gtf.parabolic.ParabolicKL(tile=T)): the nodes
@@ -779,19 +941,14 @@ k_parabolic_kl_b0(gtf_kl_graph g, gtf_kl_out o, int nblk) {
 // gathers). Record per tile (12 int32): first node, bucket-0 count, its one-edge count,
 // 0, 0, 0, bucket 0's first slot, its first pair (lo, hi), window [lo, hi), 0. The 3..4,
 // 5..8 and > 8 buckets run from gtf_kl_graph.list in the same launch, ahead of the tiles,
-// each 256-thread block as WBLOCK / BLOCK sub-blocks of the list kernel's.
-constexpr int WBLOCK = 256;
-#ifndef GTF_KL_WWIN
-#define GTF_KL_WWIN 1024
-#endif
-constexpr int WWIN = GTF_KL_WWIN;          // window nodes (gtf.parabolic.WIN_NODES)
+// each 256-thread block as WBLOCK / BLOCK sub-blocks of the list kernel's. A window node
+// takes P::Win::NODE_BYTES of LDS: 24 KB of fp64 rows and int64 ids, 12 KB of PathQ's.
 constexpr int WPT = (WWIN + WBLOCK - 1) / WBLOCK;
 constexpr int SUBS = WBLOCK / BLOCK;
-constexpr size_t sub_stage_bytes(size_t t) {
-    return stage_bytes(4, t) > stage_bytes(64, t) ? stage_bytes(4, t) : stage_bytes(64, t);
-}
-constexpr size_t win_lds_bytes(size_t t) {
-    return WWIN * 24 > SUBS * sub_stage_bytes(t) ? WWIN * 24 : SUBS * sub_stage_bytes(t);
+template <typename P>
+constexpr size_t win_lds_bytes() {
+    return (size_t)WWIN * P::Win::NODE_BYTES > SUBS * path_stage_bytes<P>() ? (size_t)WWIN * P::Win::NODE_BYTES
+                                                                            : SUBS * path_stage_bytes<P>();
 }
 #ifndef GTF_KL_WIN_WAVES
 #define GTF_KL_WIN_WAVES 5
@@ -800,11 +957,10 @@ struct WinBuckets {
     int32_t blocks[4];   // [0] tile blocks (n_blk padded to 8), [1..3] list blocks
 };
 
-template <typename T, bool STATES>
-__device__ __forceinline__ void pkl_tile(const gtf_kl_graph& g, const gtf_kl_out& o, int tile, char* lds) {
-    double* sx = (double*)lds;
-    double* sy = sx + WWIN;
-    long long* st = (long long*)(sy + WWIN);
+template <typename P, bool STATES>
+__device__ __forceinline__ void pkl_tile(const gtf_kl_graph& g, const typename P::In& c, const typename P::Out& o,
+                                         int tile, char* lds) {
+    typename P::Win win(lds);
     const int32_t* r = g.blk + 12 * (int64_t)tile;
     const int node_lo = r[0], n0 = r[1], n1 = r[2], n3 = r[3], n4 = r[4];
     const int64_t slot_lo = (int64_t)(uint32_t)r[6];
@@ -831,61 +987,64 @@ __device__ __forceinline__ void pkl_tile(const gtf_kl_graph& g, const gtf_kl_out
 #pragma unroll
         for (int q = 0; q < 4; q++) u4[q] = q < d4 ? ld_list(g.slot_src + l4 + q) : 0;
     }
-    double wx[WPT], wy[WPT];
-    long long wt[WPT];
+    typename P::XY wc[WPT];
+    typename P::Tid wt[WPT];
 #pragma unroll
     for (int j = 0; j < WPT; j++) {
         const int i = t + j * WBLOCK;
         if (i < wn) {
-            wx[j] = gx(g, wlo + i);
-            wy[j] = gy(g, wlo + i);
-            wt[j] = g.truth ? g.truth[wlo + i] : 0;
+            wc[j] = P::ld(c, wlo + i);
+            wt[j] = c.truth ? P::ldt(c, wlo + i) : 0;
         }
     }
 #pragma unroll
     for (int j = 0; j < WPT; j++) {
         const int i = t + j * WBLOCK;
-        if (i < wn) {
-            sx[i] = wx[j];
-            sy[i] = wy[j];
-            st[i] = wt[j];
-        }
+        if (i < wn) win.put(i, wc[j], wt[j]);
     }
     __syncthreads();
-    const WSrc src{&g, sx, sy, st, wlo, wlo + wn};
-    if (mine) pkl_b0_body<T, STATES>(g, o, src, node_lo + t, two, l, pair_lo + (t - n1), u0, u1);
-    else if (mine4) pkl_node4_core<T, STATES>(g, o, src, node_lo + t, (int)l4, d4, p4, u4);
+    const WSrc<P> src{c, win, wlo, wlo + wn};
+    if (mine) pkl_b0_body<P, STATES>(o, src, node_lo + t, two, l, pair_lo + (t - n1), u0, u1);
+    else if (mine4) pkl_node4_core<P, STATES>(o, src, node_lo + t, (int)l4, d4, p4, u4);
 }
 
-template <typename T, bool STATES>
+template <typename P, bool STATES>
 __global__ void __launch_bounds__(WBLOCK) __attribute__((amdgpu_waves_per_eu(GTF_KL_WIN_WAVES)))
-k_parabolic_kl_win(gtf_kl_graph g, gtf_kl_out o, WinBuckets bk) {
-    __shared__ __attribute__((aligned(16))) char lds[win_lds_bytes(sizeof(T))];
+k_parabolic_kl_win(gtf_kl_graph g, typename P::In c, typename P::Out o, WinBuckets bk) {
+    __shared__ __attribute__((aligned(16))) char lds[win_lds_bytes<P>()];
     int b = blockIdx.x;
     const int sub = (int)threadIdx.x / BLOCK, tid = (int)threadIdx.x % BLOCK;
-    char* stage = lds + sub * sub_stage_bytes(sizeof(T));
+    char* stage = lds + sub * path_stage_bytes<P>();
     if (b < bk.blocks[3]) {   // > 8 in-edges: a wavefront per node (longest-running first)
-        pkl_node<T, 64, STATES>(g, o, g.list[3], g.count[3], gtf::xcd_local(b, bk.blocks[3]) * SUBS + sub, stage, 0, tid);
+        pkl_node<P, 64, STATES>(g, c, o, g.list[3], g.count[3], gtf::xcd_local(b, bk.blocks[3]) * SUBS + sub, stage, 0, tid);
         return;
     }
     b -= bk.blocks[3];
     if (b < bk.blocks[2]) {
-        pkl_node<T, 8, STATES>(g, o, g.list[2], g.count[2], gtf::xcd_local(b, bk.blocks[2]) * SUBS + sub, stage, 0, tid);
+        pkl_node<P, 8, STATES>(g, c, o, g.list[2], g.count[2], gtf::xcd_local(b, bk.blocks[2]) * SUBS + sub, stage, 0, tid);
         return;
     }
     b -= bk.blocks[2];
     if (b < bk.blocks[1]) {
-        pkl_node4<T, STATES>(g, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]) * SUBS + sub, 0, tid);
+        pkl_node4<P, STATES>(g, c, o, g.list[1], g.count[1], gtf::xcd_local(b, bk.blocks[1]) * SUBS + sub, 0, tid);
         return;
     }
     b -= bk.blocks[1];
     const int tile = gtf::xcd_local(b, bk.blocks[0]);
     if (tile >= g.n_blk) return;   // (block-uniform: the padding to 8)
-    pkl_tile<T, STATES>(g, o, tile, lds);
+    pkl_tile<P, STATES>(g, c, o, tile, lds);
 }
 
-template <typename T>
-int launch(const gtf_kl_graph* g, const gtf_kl_out* o, hipStream_t st) {
+// full fp64 states asked for (the fp64-coordinate paths' sv / cov outputs)
+template <typename P>
+bool want_states(const typename P::Out* o) {
+    if constexpr (P::F64XY) return o->sv || o->cov;
+    else return false;
+}
+
+template <typename P>
+int launch(const gtf_kl_graph* g, const typename P::In& c, const typename P::Out* o, hipStream_t st) {
+    const bool states = want_states<P>(o);
     if (g->blk) {   // tiled layout: one block per tile record, buckets 1..3 by list
         WinBuckets wb;
         wb.blocks[0] = gtf::pad8(g->n_blk);
@@ -897,10 +1056,12 @@ int launch(const gtf_kl_graph* g, const gtf_kl_out* o, hipStream_t st) {
         }
         if (g->n_blk == 0) total -= wb.blocks[0], wb.blocks[0] = 0;
         if (total > 0) {
-            if (o->sv || o->cov)
-                hipLaunchKernelGGL((k_parabolic_kl_win<T, true>), dim3(total), dim3(WBLOCK), 0, st, *g, *o, wb);
-            else
-                hipLaunchKernelGGL((k_parabolic_kl_win<T, false>), dim3(total), dim3(WBLOCK), 0, st, *g, *o, wb);
+            if constexpr (P::F64XY) {
+                if (states)
+                    hipLaunchKernelGGL((k_parabolic_kl_win<P, true>), dim3(total), dim3(WBLOCK), 0, st, *g, c, *o, wb);
+            }
+            if (!states)
+                hipLaunchKernelGGL((k_parabolic_kl_win<P, false>), dim3(total), dim3(WBLOCK), 0, st, *g, c, *o, wb);
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
@@ -938,16 +1099,18 @@ int launch(const gtf_kl_graph* g, const gtf_kl_out* o, hipStream_t st) {
         bk.blocks[0] = 0;
     }
     if (total > 0) {
-        if (o->sv || o->cov)
-            hipLaunchKernelGGL((k_parabolic_kl<T, true>), dim3(total), dim3(BLOCK), 0, st, *g, *o, bk);
-        else
-            hipLaunchKernelGGL((k_parabolic_kl<T, false>), dim3(total), dim3(BLOCK), 0, st, *g, *o, bk);
+        if constexpr (P::F64XY) {
+            if (states) hipLaunchKernelGGL((k_parabolic_kl<P, true>), dim3(total), dim3(BLOCK), 0, st, *g, c, *o, bk);
+        }
+        if (!states) hipLaunchKernelGGL((k_parabolic_kl<P, false>), dim3(total), dim3(BLOCK), 0, st, *g, c, *o, bk);
     }
     if (b0_blocks > 0) {
-        if (o->sv || o->cov)
-            hipLaunchKernelGGL((k_parabolic_kl_b0<T, true>), dim3(b0_blocks), dim3(BLOCK), 0, st, *g, *o, b0_blocks);
-        else
-            hipLaunchKernelGGL((k_parabolic_kl_b0<T, false>), dim3(b0_blocks), dim3(BLOCK), 0, st, *g, *o, b0_blocks);
+        if constexpr (P::F64XY) {
+            if (states)
+                hipLaunchKernelGGL((k_parabolic_kl_b0<P, true>), dim3(b0_blocks), dim3(BLOCK), 0, st, *g, c, *o, b0_blocks);
+        }
+        if (!states)
+            hipLaunchKernelGGL((k_parabolic_kl_b0<P, false>), dim3(b0_blocks), dim3(BLOCK), 0, st, *g, c, *o, b0_blocks);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -957,19 +1120,23 @@ int launch(const gtf_kl_graph* g, const gtf_kl_out* o, hipStream_t st) {
     return 0;
 }
 
-}  // namespace
+int fail(const char* fn, const char* what) {
+    char m[160];
+    snprintf(m, sizeof(m), "%s: %s", fn, what);
+    gtf::set_error(m);
+    return -2;
+}
 
-extern "C" int gtf_parabolic_kl(const gtf_kl_graph* g, int32_t dtype, const gtf_kl_out* out, gtf_stream_t stream) {
-    if (!g || !out) { gtf::set_error("gtf_parabolic_kl: null argument"); return -2; }
-    if (g->n_nodes < 0 || g->n_slots < 0) { gtf::set_error("gtf_parabolic_kl: negative sizes"); return -2; }
-    if (g->blk && g->n_blk < 0) { gtf::set_error("gtf_parabolic_kl: bad block table"); return -2; }
-    int listed = 0;
+// the structure of a gtf_kl_graph -- sizes, the block table, the node lists or the ranges
+// the ordered layout implies -- checked on the host for entry point fn; listed: the nodes
+// the lists or ranges name
+int check_structure(const gtf_kl_graph* g, const char* fn, int& listed) {
+    if (g->n_nodes < 0 || g->n_slots < 0) return fail(fn, "negative sizes");
+    if (g->blk && g->n_blk < 0) return fail(fn, "bad block table");
+    listed = 0;
     const bool ordered = !g->blk && !g->list[0] && !g->list[1] && !g->list[2] && !g->list[3];
     for (int i = g->blk ? 1 : 0; i < 4; i++) {
-        if (g->count[i] < 0 || (g->count[i] > 0 && !g->list[i] && !ordered)) {
-            gtf::set_error("gtf_parabolic_kl: bad node list");
-            return -2;
-        }
+        if (g->count[i] < 0 || (g->count[i] > 0 && !g->list[i] && !ordered)) return fail(fn, "bad node list");
         listed += g->count[i];
     }
     if (ordered) {   // every address the ordered layout implies stays inside the arrays
@@ -990,24 +1157,42 @@ extern "C" int gtf_parabolic_kl(const gtf_kl_graph* g, int32_t dtype, const gtf_
         } else if (g->deg_runs != 0) {
             ok = false;
         }
-        if (!ok) { gtf::set_error("gtf_parabolic_kl: bad ordered layout"); return -2; }
+        if (!ok) return fail(fn, "bad ordered layout");
     }
-    if (g->gnn_stride != 0 && g->gnn_stride != 2 && g->gnn_stride != 4) {
-        gtf::set_error("gtf_parabolic_kl: gnn_stride must be 0, 2 or 4");
-        return -2;
-    }
-    if ((listed || (g->blk && g->n_blk > 0)) && (!g->slot_ptr || !g->slot_src || !g->gnn || !g->pair_ptr || !out->kl)) {
-        gtf::set_error("gtf_parabolic_kl: missing arrays");
-        return -2;
-    }
-    if ((out->sv == nullptr) != (out->cov == nullptr)) {
-        gtf::set_error("gtf_parabolic_kl: sv and cov outputs go together");
-        return -2;
-    }
-    if (out->truth && !g->truth) { gtf::set_error("gtf_parabolic_kl: truth output needs graph truth"); return -2; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gtf_parabolic_kl(const gtf_kl_graph* g, int32_t dtype, const gtf_kl_out* out, gtf_stream_t stream) {
+    const char* fn = "gtf_parabolic_kl";
+    if (!g || !out) return fail(fn, "null argument");
+    int listed = 0;
+    if (const int rc = check_structure(g, fn, listed)) return rc;
+    if (g->gnn_stride != 0 && g->gnn_stride != 2 && g->gnn_stride != 4) return fail(fn, "gnn_stride must be 0, 2 or 4");
+    if ((listed || (g->blk && g->n_blk > 0)) && (!g->slot_ptr || !g->slot_src || !g->gnn || !g->pair_ptr || !out->kl))
+        return fail(fn, "missing arrays");
+    if ((out->sv == nullptr) != (out->cov == nullptr)) return fail(fn, "sv and cov outputs go together");
+    if (out->truth && !g->truth) return fail(fn, "truth output needs graph truth");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == GTF_F64) return launch<double>(g, out, st);
-    if (dtype == GTF_F32) return launch<float>(g, out, st);
-    gtf::set_error("gtf_parabolic_kl: dtype must be GTF_F64 or GTF_F32");
-    return -2;
+    const DblIn c{g->gnn, (int64_t)(g->gnn_stride ? g->gnn_stride : 4), g->truth};
+    if (dtype == GTF_F64) return launch<PathD<double>>(g, c, out, st);
+    if (dtype == GTF_F32) return launch<PathD<float>>(g, c, out, st);
+    return fail(fn, "dtype must be GTF_F64 or GTF_F32");
+}
+
+extern "C" int gtf_parabolic_kl_q32(const gtf_kl_graph* g, const gtf_kl_q32* q, const gtf_kl_out32* out,
+                                    gtf_stream_t stream) {
+    const char* fn = "gtf_parabolic_kl_q32";
+    if (!g || !q || !out) return fail(fn, "null argument");
+    const float s = (float)q->scale;   // (a power of two by the quantisation rule: exact in fp32)
+    if (!(q->scale > 0.0) || !isfinite(q->scale) || !(s > 0.0f) || !isfinite(s))
+        return fail(fn, "scale must be finite and > 0");
+    int listed = 0;
+    if (const int rc = check_structure(g, fn, listed)) return rc;
+    if ((listed || (g->blk && g->n_blk > 0)) && (!g->slot_ptr || !g->slot_src || !q->xy || !g->pair_ptr || !out->kl))
+        return fail(fn, "missing arrays");
+    if (out->truth && !q->truth32) return fail(fn, "truth output needs truth32");
+    const Q32In c{(const int2*)q->xy, q->truth32, s};
+    return launch<PathQ>(g, c, out, (hipStream_t)stream);
 }

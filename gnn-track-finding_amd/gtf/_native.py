@@ -123,6 +123,14 @@ class GtfKlOut(ctypes.Structure):
     _fields_ = [("kl", P), ("truth", P), ("emp_var", P), ("emp_mean", P), ("sv", P), ("cov", P), ("err", P)]
 
 
+class GtfKlQ32(ctypes.Structure):
+    _fields_ = [("xy", P), ("scale", ctypes.c_double), ("truth32", P)]
+
+
+class GtfKlOut32(ctypes.Structure):
+    _fields_ = [("kl", P), ("truth", P), ("emp_var", P), ("emp_mean", P), ("err", P)]
+
+
 GTF_F64, GTF_F32 = 0, 1
 
 ERR_FLAGS = {
@@ -142,7 +150,7 @@ ERR_FLAGS = {
 # exported symbols (must match include/gtf.h; tests check the .so exports all of them)
 SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "gtf_clear_errors", "gtf_read_errors", "gtf_extrapolate", "gtf_update",
            "gtf_message_passing", "gtf_node_ops",
-           "gtf_cluster", "gtf_pass", "gtf_pass_ev", "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_tag_workspace_bytes", "gtf_tag_propagate", "gtf_parabolic_kl", "gtf_track_state_estimates", "gtf_pass_shard",
+           "gtf_cluster", "gtf_pass", "gtf_pass_ev", "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_tag_workspace_bytes", "gtf_tag_propagate", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_pass_shard",
            "gtf_shard_chunk_bytes", "gtf_shard_pack", "gtf_shard_unpack", "gtf_halo_pack", "gtf_halo_unpack",
            "gtf_extract_workspace_bytes",
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
@@ -225,6 +233,8 @@ def lib(lean: bool = False):
     L.gtf_halo_unpack.argtypes = [N, E, HA, P, P]
     L.gtf_track_state_estimates.argtypes = [G, S, ctypes.POINTER(GtfTseExtra), PR, P]
     L.gtf_parabolic_kl.argtypes = [ctypes.POINTER(GtfKlGraph), I32, ctypes.POINTER(GtfKlOut), P]
+    L.gtf_parabolic_kl_q32.argtypes = [ctypes.POINTER(GtfKlGraph), ctypes.POINTER(GtfKlQ32),
+                                       ctypes.POINTER(GtfKlOut32), P]
     L.gtf_build_event_csr.argtypes = [ctypes.POINTER(GtfEventCsr)]
     L.gtf_build_event_device_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_build_event_device_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -257,7 +267,7 @@ def lib(lean: bool = False):
     L.gtf_version.restype = ctypes.c_char_p
     for fn in ("gtf_workspace_init", "gtf_uts_materialize", "gtf_clear_errors", "gtf_read_errors", "gtf_extrapolate", "gtf_update", "gtf_cluster", "gtf_pass",
                "gtf_pass_ev", "gtf_message_passing", "gtf_node_ops",
-               "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_parabolic_kl", "gtf_track_state_estimates", "gtf_pass_shard", "gtf_shard_pack",
+               "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_pass_shard", "gtf_shard_pack",
                "gtf_shard_unpack", "gtf_halo_pack", "gtf_halo_unpack", "gtf_extract_candidates", "gtf_build_event_csr",
                "gtf_candidate_order", "gtf_updated_state_pair_counts", "gtf_updated_state_distances",
                "gtf_set_diagnostics", "gtf_build_event_csr_device", "gtf_device_init", "gtf_malloc", "gtf_free",

@@ -37,6 +37,32 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def quantise_xy(gnn, scale=None):
+    """(q [N, 2] int32, scale): the x, y columns of ``gnn`` as 32-bit fixed point, the
+    compact input of gtf_parabolic_kl_q32 (include/gtf.h). scale = 2^(e - 30) with e the
+    smallest integer such that every |x|, |y| < 2^e, and q = rint(xy / scale): every
+    |q| < 2^30 (the difference of two coordinates is then an exact int32), q * scale is
+    exact in fp64 and within scale / 2 of the input. A given ``scale`` (a replica keeps its
+    parent's) is used as it is; coordinates that do not fit it raise ValueError."""
+    xy = np.asarray(gnn, np.float64)
+    xy = xy.reshape(-1, xy.shape[-1] if xy.ndim > 1 else 2)[:, :2]   # ([N, 2], [N, 4] or flat x, y pairs)
+    if not np.isfinite(xy).all():
+        raise ValueError("quantise_xy: non-finite coordinate")
+    m = float(np.abs(xy).max()) if xy.size else 0.0
+    if scale is None:
+        e = int(np.frexp(m)[1]) if m > 0.0 else 0   # m = f * 2^e with 0.5 <= f < 1: 2^(e - 1) <= m < 2^e
+        if np.rint(np.ldexp(m, 30 - e)) >= 2.0 ** 30:   # (within half a step of 2^e: it would round to 2^30)
+            e += 1
+        scale = float(np.ldexp(1.0, e - 30))
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError("quantise_xy: scale must be finite and > 0")
+    q = np.rint(xy / scale)
+    if q.size and np.abs(q).max() >= 2.0 ** 30:
+        raise ValueError("quantise_xy: max |x|, |y| = %g does not fit scale %g (|q| < 2^30)" % (m, scale))
+    return np.ascontiguousarray(q.astype(np.int32)), scale
+
+
 def in_edge_csr(g: TrackGraph):
     """(slot_ptr, slot_src) of the graph's in-edges (slots that are edges)."""
     ise = g.slot["is_edge"].astype(bool)
@@ -65,10 +91,16 @@ class ParabolicKL:
     between them, each tile with its bucket-0 nodes first: one 256-thread block per tile
     record (gtf_kl_graph.blk) loads its nodes' sender lists and the coordinates of a window
     of consecutive nodes around the tile -- where a hit's neighbours lie -- in one round,
-    and reads the neighbours from LDS. The 3..4, 5..8 and > 8 buckets go by node list."""
+    and reads the neighbours from LDS. The 3..4, 5..8 and > 8 buckets go by node list.
+
+    compact: additionally upload the coordinates as 32-bit fixed point (quantise_xy) with
+    their scale, and the truth ids as int32 (ids beyond int32 relabelled densely: only their
+    equality matters), for run(out, "q32") -- gtf_parabolic_kl_q32, 12
+    bytes per node instead of 24, fp32 arithmetic. The structure arrays are shared with the
+    fp64 path; without compact the object and its device footprint are unchanged."""
 
     def __init__(self, slot_ptr, slot_src, gnn, truth=None, device="cuda", with_single=False, ordered=False,
-                 tile=0, sort_window=8192, tile_b1=True):
+                 tile=0, sort_window=8192, tile_b1=True, compact=False):
         slot_ptr = np.ascontiguousarray(slot_ptr, np.int32)
         self.n_nodes = int(slot_ptr.shape[0] - 1)
         self.n_slots = int(slot_ptr[-1])
@@ -134,6 +166,9 @@ class ParabolicKL:
         self.lists = [t(x) for x in lists]
         self.device = dev
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.q = self.truth32 = self.scale = self._q = None
+        if compact:
+            self._set_compact(np.asarray(gnn, np.float64).reshape(-1, 4), truth)
         if self.tile > 0:   # one block record per tile (gtf_kl_graph.blk); buckets 1..3 by list
             blk = self._block_table(d, pair_ptr)
             self.blk = t(blk)
@@ -162,6 +197,19 @@ class ParabolicKL:
                                      _ptr(self.gnn), _ptr(self.truth), _ptr(self.pair_ptr),
                                      (ctypes.c_void_p * 4)(*[x.data_ptr() if x.numel() else None for x in self.lists]),
                                      (ctypes.c_int32 * 4)(*[x.numel() for x in self.lists]), gnn_stride=2)
+
+    def _set_compact(self, gnn, truth, scale=None):
+        """upload the fixed-point coordinates (device node order) and int32 truth ids"""
+        q, self.scale = quantise_xy(np.asarray(gnn, np.float64)[:, :2], scale)
+        self.q = torch.from_numpy(q).to(self.device)
+        if truth is not None and self.truth32 is None:
+            # the kernel only compares ids: those that fit int32 go as they are, others (TrackML
+            # particle ids are 60-bit numbers) as dense labels, equal exactly where the ids are
+            t64 = np.asarray(truth, np.int64)
+            if t64.size and (t64.min() < -2**31 or t64.max() >= 2**31):
+                t64 = np.unique(t64, return_inverse=True)[1].reshape(-1)
+            self.truth32 = torch.from_numpy(np.ascontiguousarray(t64.astype(np.int32))).to(self.device)
+        self._q = nat.GtfKlQ32(_ptr(self.q), self.scale, _ptr(self.truth32))
 
     def _block_table(self, d, pair_ptr, margin=WIN_MARGIN):   # (rank < 16: 10 keys)
         """gtf_kl_graph.blk of the tiled layout: one record of 12 int32 per tile (first node,
@@ -216,6 +264,13 @@ class ParabolicKL:
             if self.node_of is not None:
                 gh = gh[self.node_of]
             r.gnn = torch.from_numpy(np.ascontiguousarray(gh)).to(self.device)
+        if self.q is not None:   # the compact copy: re-quantised with the parent's scale
+            r.truth32 = cl(self.truth32)
+            if gnn is None:
+                r.q = cl(self.q)
+                r._q = nat.GtfKlQ32(_ptr(r.q), r.scale, _ptr(r.truth32))
+            else:
+                r._set_compact(gh, None, self.scale)
         g = nat.GtfKlGraph.from_buffer_copy(self._g)
         g.slot_ptr, g.slot_src, g.gnn = _ptr(r.slot_ptr), _ptr(r.slot_src), _ptr(r.gnn)
         g.truth, g.pair_ptr = _ptr(r.truth), _ptr(r.pair_ptr)
@@ -227,9 +282,12 @@ class ParabolicKL:
         r._g = g
         return r
 
-    def footprint_bytes(self, out) -> int:
-        """device bytes of this batch's inputs and the outputs in ``out``"""
-        ts = [self.slot_ptr, self.slot_src, self.gnn, self.truth, self.pair_ptr] + list(self.lists)
+    def footprint_bytes(self, out, dtype=None) -> int:
+        """device bytes of this batch's inputs and the outputs in ``out``: of the coordinate
+        and truth arrays, those the path of ``dtype`` touches ("q32": the fixed-point copy and
+        the int32 ids; default: the fp64 rows and int64 ids)"""
+        coords = [self.q, self.truth32] if dtype == "q32" else [self.gnn, self.truth]
+        ts = [self.slot_ptr, self.slot_src, self.pair_ptr] + coords + list(self.lists)
         ts += [v for k, v in out.items() if k not in ("kl", "truth")]   # (views of _kl / _truth)
         seen, tot = set(), 0
         for t in ts:
@@ -245,7 +303,12 @@ class ParabolicKL:
         return cls(ptr, src, g.node["gnn"], truth, device, with_single)
 
     def alloc(self, dtype="f64", truth=True, emp=True, states=False):
+        if dtype not in ("f64", "f32", "q32"):
+            raise ValueError("dtype must be 'f64', 'f32' or 'q32'")
+        if dtype == "q32" and states:
+            raise ValueError("the q32 path has no sv / cov outputs (full states are fp64: dtype='f64')")
         f = torch.float64 if dtype == "f64" else torch.float32
+        fm = torch.float32 if dtype == "q32" else torch.float64   # the gradient moments
         # pair buffers hold >= 1 element so their pointers are never null, even with no
         # pairs (the C-ABI rejects null outputs); "kl"/"truth" are views of the pair count
         z = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=self.device)  # noqa: E731
@@ -255,17 +318,29 @@ class ParabolicKL:
             out["_truth"] = z(self.n_pairs, torch.int8)
             out["truth"] = out["_truth"][:self.n_pairs]
         if emp:     # True: gradient mean and variance; "var": variance only (the training rows)
-            out["emp_var"] = torch.full((self.n_nodes,), float("nan"), dtype=torch.float64, device=self.device)
+            out["emp_var"] = torch.full((self.n_nodes,), float("nan"), dtype=fm, device=self.device)
             if emp is True:
-                out["emp_mean"] = torch.full((self.n_nodes,), float("nan"), dtype=torch.float64,
-                                             device=self.device)
+                out["emp_mean"] = torch.full((self.n_nodes,), float("nan"), dtype=fm, device=self.device)
         if states:
             out["sv"] = torch.full((self.n_slots, 3), float("nan"), dtype=torch.float64, device=self.device)
             out["cov"] = torch.full((self.n_slots, 3, 3), float("nan"), dtype=torch.float64, device=self.device)
         return out
 
     def run(self, out, dtype="f64", stream=None):
-        """launch gtf_parabolic_kl into the buffers of ``alloc`` (stream-ordered)."""
+        """launch gtf_parabolic_kl -- dtype "q32": gtf_parabolic_kl_q32 -- into the buffers of
+        ``alloc`` for the same dtype (stream-ordered)."""
+        if dtype == "q32":
+            if self._q is None:
+                raise ValueError("run(out, 'q32') needs ParabolicKL(..., compact=True)")
+            if out["_kl"].dtype != torch.float32 or "sv" in out or any(
+                    k in out and out[k].dtype != torch.float32 for k in ("emp_var", "emp_mean")):
+                raise ValueError("run(out, 'q32') needs the buffers of alloc('q32')")
+            o = nat.GtfKlOut32(_ptr(out["_kl"]), _ptr(out.get("_truth")), _ptr(out.get("emp_var")),
+                               _ptr(out.get("emp_mean")), _ptr(self.err))
+            s = stream if stream is not None else torch.cuda.current_stream(self.device)
+            nat.check(nat.lib().gtf_parabolic_kl_q32(ctypes.byref(self._g), ctypes.byref(self._q), ctypes.byref(o),
+                                                     ctypes.c_void_p(s.cuda_stream)))
+            return out
         o = nat.GtfKlOut(_ptr(out["_kl"]), _ptr(out.get("_truth")), _ptr(out.get("emp_var")),
                          _ptr(out.get("emp_mean")), _ptr(out.get("sv")), _ptr(out.get("cov")), _ptr(self.err))
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
@@ -311,13 +386,13 @@ class ParabolicKL:
 
 def training_rows(g: TrackGraph, truth=None, dtype="f64", device="cuda"):
     """(node, i, j, kl_dist, emp_var, truth) rows of extract_metadata_trackml_parabolic_model.py
-    for one event graph, computed on the GPU."""
+    for one event graph, computed on the GPU (dtype "f64", "f32" or the compact "q32")."""
     ptr, src = in_edge_csr(g)
     return training_rows_csr(ptr, src, g.node["gnn"], truth, dtype, device)
 
 
 def training_rows_csr(slot_ptr, slot_src, gnn, truth=None, dtype="f64", device="cuda"):
-    k = ParabolicKL(slot_ptr, slot_src, gnn, truth, device)
+    k = ParabolicKL(slot_ptr, slot_src, gnn, truth, device, compact=dtype == "q32")
     out = k.run(k.alloc(dtype, truth=truth is not None, emp="var"), dtype)
     node, i, j = k.pair_index()
     ev = out["emp_var"].cpu().numpy()[node]

@@ -31,10 +31,13 @@ Parabolic-model KL kernel (gtf_parabolic_kl, §8 a17), minimal unique traffic:
     written, plus its own coordinates counted above;
   * 4 B per in-edge (slot_src);
   * 9 B per pair in fp64 (distance 8 + truth flag 1), 5 B in fp32.
+The compact path ("q32", gtf_parabolic_kl_q32): 12 B per node (int32 x, y 8 + int32 truth
+id 4), 24 B per listed node (emp_var is a float), 4 B per in-edge, 5 B per pair.
 """
 
 PKL_PER_NODE, PKL_PER_LISTED, PKL_PER_SLOT = 24, 28, 4
-PKL_PER_PAIR = {"f64": 9, "f32": 5}
+PKL_PER_PAIR = {"f64": 9, "f32": 5, "q32": 5}
+PKL_Q32_PER_NODE, PKL_Q32_PER_LISTED = 12, 24
 
 EXTRAP_PER_EDGE, EXTRAP_PER_NODE = 94, 104
 REWEIGHT_PER_SLOT, REWEIGHT_PER_NODE = 100, 6
@@ -72,6 +75,9 @@ def pass_bytes(n_edges, n_nodes):
 
 
 def parabolic_kl_bytes(n_nodes, n_listed, n_slots, n_pairs, dtype="f64"):
+    if dtype == "q32":
+        return (PKL_Q32_PER_NODE * n_nodes + PKL_Q32_PER_LISTED * n_listed + PKL_PER_SLOT * n_slots
+                + PKL_PER_PAIR[dtype] * n_pairs)
     return (PKL_PER_NODE * n_nodes + PKL_PER_LISTED * n_listed + PKL_PER_SLOT * n_slots
             + PKL_PER_PAIR[dtype] * n_pairs)
 

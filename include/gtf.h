@@ -657,6 +657,36 @@ typedef struct gtf_kl_out {
  * config-5 tolerance sweep). sv/cov outputs are fp64 in both modes. */
 int gtf_parabolic_kl(const gtf_kl_graph* g, int32_t dtype, const gtf_kl_out* out, gtf_stream_t stream);
 
+/* Compact input mode (gtf.parabolic.ParabolicKL(compact=True)): the same states, distances,
+ * gradient moments and truth flags (utils.py:221-289) from 32-bit fixed-point coordinates
+ * and int32 truth ids -- 12 bytes per node where gtf_kl_graph's fp64 x, y and int64 id take
+ * 24 -- computed in fp32 throughout.
+ * Quantisation rule (gtf.parabolic.quantise_xy): scale = 2^(e - 30) with e the smallest
+ * integer such that every |x|, |y| < 2^e, and q = rint(x / scale), so every |q| < 2^30 and
+ * q * scale is within scale / 2 of x. |q| < 2^30 is REQUIRED of the caller (it is not
+ * checked: the coordinates live in device memory): the difference of two coordinates then
+ * fits an int32 exactly, so the kernel translates a neighbour to its node in integers with
+ * no rounding and only the differences, not the coordinates, are rounded to fp32. (Plain
+ * fp32 coordinates lose that: their rounding alone costs the fp32 mode's error bar.) */
+typedef struct gtf_kl_q32 {
+    const int32_t* xy;       /* [N*2] (qx, qy) per node, 8-byte aligned; x = qx * scale, y = qy * scale */
+    double scale;            /* finite, > 0; a power of two by the rule above */
+    const int32_t* truth32;  /* [N] truth_particle, or NULL */
+} gtf_kl_q32;
+
+typedef struct gtf_kl_out32 {
+    float* kl;         /* [P] */
+    int8_t* truth;     /* [P] or NULL (needs q->truth32) */
+    float* emp_var;    /* [N] or NULL; np.var of the gradients dqy / dqx, summed in fp64, stored as float */
+    float* emp_mean;   /* [N] or NULL; np.mean of the gradients */
+    uint32_t* err;     /* device error word (GTF_ERR_SINGULAR_H) or NULL */
+} gtf_kl_out32;        /* (no sv / cov: full states are an fp64 service of gtf_parabolic_kl) */
+
+/* g supplies the structure only -- the CSR, pair_ptr, the lists or the ordered / degree-run
+ * fields, blk -- in any of gtf_kl_graph's three layouts; g->gnn, g->gnn_stride and g->truth
+ * are ignored. Pairs, moments and the error word are laid out as gtf_parabolic_kl's. */
+int gtf_parabolic_kl_q32(const gtf_kl_graph* g, const gtf_kl_q32* q, const gtf_kl_out32* out, gtf_stream_t stream);
+
 /* ---- event conversion: CSV rows -> packed CSR in the reference's orders -------------
  * Replaces helper.construct_graph + nx.DiGraph + the weakly-connected-component
  * subgraph copies of event_conversion.py:63-84 (helper.py:465-521) and the key order of

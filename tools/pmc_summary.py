@@ -29,6 +29,11 @@ NAMES = {
     "k_parabolic_kl<double, false>": "k_parabolic_kl (fp64)",
     "k_parabolic_kl<float, false>": "k_parabolic_kl (fp32)",
     "k_parabolic_kl_win<double, false>": "k_parabolic_kl_win (fp64, tiled layout)",
+    # (the kernels are templates over an input path since the compact q32 mode)
+    "k_parabolic_kl<PathD<double>, false>": "k_parabolic_kl (fp64)",
+    "k_parabolic_kl<PathD<float>, false>": "k_parabolic_kl (fp32)",
+    "k_parabolic_kl<PathQ, false>": "k_parabolic_kl (q32)",
+    "k_parabolic_kl_win<PathD<double>, false>": "k_parabolic_kl_win (fp64, tiled layout)",
 }
 
 
