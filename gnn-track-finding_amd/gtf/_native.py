@@ -40,6 +40,13 @@ class GtfGraph(ctypes.Structure):
         self.abi_version = ABI_VERSION
 
 
+class GtfGraphTables(ctypes.Structure):
+    """gtf_graph_tables: the caller-allocated outputs of gtf_graph_prepare (NULL = not wanted)"""
+    _fields_ = [("slot_dst", P), ("out_dst", P), ("slot_layer", P), ("slot_outpos", P), ("slot_outidx", P),
+                ("slot_class", P), ("slot_sflags", P), ("slot_xclass", P), ("slot_sxzr", P), ("slot_static", P),
+                ("sched", P), ("sched_seg", P), ("out_sched", P), ("out_lanes", P)]
+
+
 class GtfNodes(ctypes.Structure):
     _fields_ = [("has_merged", P), ("merged_state", P), ("merged_cov", P), ("merged_prior", P),
                 ("has_tse", P), ("has_uts", P), ("degree", P)]
@@ -155,6 +162,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_workspace_bytes",
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
+           "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_updated_state_pair_counts", "gtf_updated_state_distances", "gtf_set_diagnostics",
            "gtf_device_init", "gtf_malloc", "gtf_free", "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod",
            "gtf_memset", "gtf_stream_synchronize",
@@ -239,6 +247,9 @@ def lib(lean: bool = False):
     L.gtf_build_event_device_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_build_event_device_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     L.gtf_build_event_csr_device.argtypes = [ctypes.POINTER(GtfEventCsr), P, ctypes.c_size_t, P]
+    L.gtf_graph_prepare_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_graph_prepare_workspace_bytes.argtypes = [I32, I32, I32]
+    L.gtf_graph_prepare.argtypes = [G, ctypes.POINTER(GtfGraphTables), P, ctypes.c_size_t, P]
     L.gtf_candidate_order.argtypes = [ctypes.POINTER(GtfCandidateGraph), P]
     L.gtf_updated_state_pair_counts.argtypes = [G, N, S, E, P, P]
     L.gtf_updated_state_distances.argtypes = [G, N, S, E, P, P, ctypes.POINTER(GtfPairOut), P]
@@ -274,7 +285,7 @@ def lib(lean: bool = False):
                "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod", "gtf_memset", "gtf_stream_synchronize",
                "gtf_comm_unique_id", "gtf_comm_init", "gtf_comm_destroy", "gtf_comm_rank", "gtf_comm_size",
                "gtf_halo_exchange", "gtf_halo_alltoall", "gtf_allreduce_max_i64", "gtf_allgather_bytes",
-               "gtf_tag_propagate_shard"):
+               "gtf_tag_propagate_shard", "gtf_graph_prepare"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

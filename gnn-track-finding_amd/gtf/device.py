@@ -240,14 +240,23 @@ class DeviceGraph:
     stage methods are layout-independent (the pass is equivariant under renumber)."""
 
     def __init__(self, g: TrackGraph, device: str = "cuda", schedule: bool = True, layout: str = "natural",
-                 pack: bool = False, tile: int = TILE, mem: str = "torch", classes=None):
+                 pack: bool = False, tile: int = TILE, mem: str = "torch", classes=None, tables: str = "host"):
         """mem "torch": the arrays are torch tensors (every method). mem "hip": plain
         allocations from libgtf (gtf.devmem, no torch in the process): the stage methods,
         clear_errors / errors and download only -- the drop-in CLIs' path. classes: upload
         the graph-static slot classes (gtf_graph.slot_class); None = on graphs of at least
-        CLASS_MIN_SLOTS slots."""
+        CLASS_MIN_SLOTS slots. tables "host": the schedules and slot tables are built by the NumPy
+        builders of this module and uploaded. tables "device": only the base arrays are uploaded
+        and gtf_graph_prepare (include/gtf.h) builds the same tables on the GPU, from the
+        (possibly renumbered) graph; classes=None then means on (the host cost behind
+        CLASS_MIN_SLOTS is gone). Not with layout "padded" or pack=True."""
         if mem not in ("torch", "hip"):
             raise ValueError("mem must be 'torch' or 'hip'")
+        if tables not in ("host", "device"):
+            raise ValueError("tables must be 'host' or 'device'")
+        if tables == "device" and (layout == "padded" or pack):
+            raise ValueError("tables='device' builds neither the padded layout nor the packed schedule: "
+                             "use tables='host' with layout='padded' or pack=True")
         self.mem = mem
         torch = _torch() if mem == "torch" else None
         self.layout = layout
@@ -275,6 +284,15 @@ class DeviceGraph:
         up("slot_ptr", g.slot_ptr.astype(np.int32))
         up("out_ptr", g.out_ptr.astype(np.int32))
         up("out_slot", g.out_slot.astype(np.int32))
+        # tables "device": gtf_graph_prepare builds them (a graph without nodes, or without
+        # slots and edges, has nothing to build there: its few tables come from the host)
+        self.tables = tables
+        dev_tables = tables == "device" and g.n_nodes > 0 and (g.n_slots > 0 or g.n_edges > 0)
+        if dev_tables:
+            self._upload_rest(g, pack)
+            self._device_tables(g, classes, schedule)
+            self._finish(g, pack)
+            return
         up("slot_dst", g.slot_dst().astype(np.int32))
         out_dst = g.slot_dst()[g.out_slot].astype(np.int32) if g.n_edges else np.zeros(0, np.int32)
         up("out_dst", out_dst)
@@ -339,6 +357,20 @@ class DeviceGraph:
             self.n_pack_waves = int(pwave.size - 1)
         self.n_g = self.n_g_all if schedule else [0] * len(BUCKETS)
         self.use_sched = schedule
+        self._upload_rest(g, pack)
+        self._finish(g, pack)
+
+    def _upload_rest(self, g: TrackGraph, pack):
+        """solo and the node and slot arrays of the graph (no schedule, no slot table)"""
+        up = self._up
+        if "solo" not in self.t:
+            sub = g.node["sub_id"].astype(np.int64)
+            if g.n_nodes:
+                sizes = np.bincount(sub - sub.min())
+                solo = (sizes[sub - sub.min()] == 1).astype(np.uint8)
+            else:
+                solo = np.zeros(0, np.uint8)
+            up("solo", solo)
         for f in ("gnn", "xyzr", "layer") + MUTABLE_NODE:
             up(f, g.node[f])
         for f in SLOT_FIELDS:
@@ -348,6 +380,10 @@ class DeviceGraph:
                 up(f, ((g.slot[f] != 0).astype(np.uint8) | (live_coordinates(g).astype(np.uint8) << 1)))
                 continue
             up(f, g.slot[f])
+
+    def _finish(self, g: TrackGraph, pack):
+        """the arena, the workspace and the C structs"""
+        torch = self.torch
         self._staged, self._resident = [], None   # stage_inputs() copies
         ws_bytes = int(self.lib.gtf_workspace_bytes(g.n_nodes, g.n_slots))
         if torch is not None:
@@ -361,6 +397,53 @@ class DeviceGraph:
             for t in self.t.values():
                 t._pending = None
         self._build_structs(pack)
+
+    def _device_tables(self, g: TrackGraph, classes, schedule):
+        """tables "device": allocate the schedules and slot tables, have gtf_graph_prepare fill
+        them from the uploaded base arrays, and take the bucket counts from the struct it filled"""
+        import os
+        N, S, E = g.n_nodes, g.n_slots, g.n_edges
+        self.use_outidx = os.environ.get("GTF_NO_OUTIDX", "0") != "1"
+        self.use_classes = (classes if classes is not None else True) and os.environ.get("GTF_NO_CLASSES", "0") != "1"
+        self.use_sxzr = self.use_classes and os.environ.get("GTF_NO_SXZR", "0") != "1"
+        self.use_static32 = self.use_classes and os.environ.get("GTF_NO_STATIC32", "0") != "1"
+        want = [("slot_dst", S, np.int32), ("out_dst", E, np.int32), ("slot_layer", S, np.float64),
+                ("slot_outpos", S, np.int32), ("slot_outidx", S, np.int32), ("sched", N, np.int32),
+                ("sched_seg", 2 * N, np.int32), ("out_sched", 4 * N, np.int32), ("out_lanes", 16 * N, np.int32)]
+        if self.use_classes:
+            want += [("slot_class", S, np.int64), ("slot_sflags", S, np.uint8), ("slot_xclass", S, np.int64)]
+        if self.use_sxzr:
+            want.append(("slot_sxzr", 3 * S, np.float64))
+        if self.use_static32:
+            want.append(("slot_static", S, np.int32))
+        for name, n, dt in want:
+            self.t[name] = self._dev_empty(n, dt)
+        ws = self._dev_empty(int(self.lib.gtf_graph_prepare_workspace_bytes(N, S, E)), np.uint8)
+        p = self.ptr
+        cg = nat.GtfGraph(n_nodes=N, n_slots=S, n_edges=E, slot_ptr=p("slot_ptr"), slot_src=p("slot_src"),
+                          out_ptr=p("out_ptr"), out_slot=p("out_slot"), is_edge=p("is_edge"), rev_edge=p("rev_edge"),
+                          gnn=p("gnn"), layer=p("layer"))
+        tb = nat.GtfGraphTables(**{name: p(name) for name, _, _ in want})
+        nat.check(self.lib.gtf_graph_prepare(ctypes.byref(cg), ctypes.byref(tb), ctypes.c_void_p(ws.data_ptr()),
+                                             ctypes.c_size_t(ws.numel()), self.stream))
+        # the slot and out-edge kernels are still in flight and the workspace goes out of scope
+        # here: a torch allocation is reused in stream order, a plain one is freed at once
+        if self.torch is None:
+            nat.check(self.lib.gtf_stream_synchronize(None))
+        self.n_g_all = [cg.n_g4, cg.n_g8, cg.n_g16, cg.n_g32, cg.n_g64]
+        self.n_big = cg.n_big
+        self.n_g2, self.n_g6, self.n_g12 = cg.n_g2, cg.n_g6, cg.n_g12
+        self.n_o = [cg.n_o4, cg.n_o8, cg.n_o16]
+        self.n_pack_waves = 0
+        self.n_g = self.n_g_all if schedule else [0] * len(BUCKETS)
+        self.use_sched = schedule
+
+    def _dev_empty(self, n, dtype):
+        """an uninitialised device array of this graph's allocator"""
+        if self.torch is None:
+            from .devmem import HipArray
+            return HipArray(n, dtype)
+        return self.torch.empty(n, dtype=getattr(self.torch, np.dtype(dtype).name), device=self.device)
 
     # ---------------------------------------------------------------- memory
     def _make_arena(self, names):

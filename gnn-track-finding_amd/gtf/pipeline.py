@@ -86,17 +86,18 @@ def event_layout(event_prefix: str, min_volume: int, max_volume: int, builder: s
 
 
 def build_event(event_prefix: str, min_volume: int, max_volume: int, p: Params = None, device="cuda",
-                builder: str = "device"):
+                builder: str = "device", tables: str = "host"):
     """event_conversion.py:53-101: CSVs -> packed network with track_state_estimates,
     activation 1, priors, mixture weights and degrees, all on the GPU (the graph build by
     gtf_build_event_csr_device; builder "native" for the host C++ one, the same arrays).
+    tables: DeviceGraph's ("device": the schedules and slot tables by gtf_graph_prepare).
     Returns (graph, vivl[N, 2])."""
     from .device import DeviceGraph
     p = p or Params()
     g, vivl = event_layout(event_prefix, min_volume, max_volume, builder, device)
     if g.n_nodes == 0:
         return g, vivl
-    d = DeviceGraph(g, device)
+    d = DeviceGraph(g, device, tables=tables)
     d.clear_errors()
     d.track_state_estimates(p)
     d.node_ops(["priors_tse", "mw_tse", "degree"], p)
@@ -111,11 +112,12 @@ def _ids(g: TrackGraph, groups):
 
 
 def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
-        device="cuda", first: int = 1, keep_graphs: bool = False) -> List[Iteration]:
+        device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host") -> List[Iteration]:
     """Iterations ``first`` .. ``first + iterations - 1`` of the loop, starting from
     the stage input ``g`` (the event network for iteration 1). Stops early when
     nothing remains. keep_graphs: also return each iteration's stage output and
-    remaining graphs (for saving, gtf.store)."""
+    remaining graphs (for saving, gtf.store). tables: passed to every DeviceGraph ("device":
+    the schedules and slot tables by gtf_graph_prepare instead of the host builders)."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
@@ -128,7 +130,7 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
         if g.n_nodes == 0:
             break
         t0 = time.perf_counter()
-        d = DeviceGraph(g, device)
+        d = DeviceGraph(g, device, tables=tables)
         torch = d.torch
         d.clear_errors()
         if it == 1:
@@ -157,7 +159,7 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
         refresh_send_mw(nxt)
         if it % 2 == 0 and nxt.n_nodes:
             # remove_state_metadata.py on the remaining directory (run_gnn_trackml_mod.sh:137-139)
-            du = DeviceGraph(nxt, device)
+            du = DeviceGraph(nxt, device, tables=tables)
             du.clear_errors()
             du.update(p)
             du.raise_errors()

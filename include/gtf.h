@@ -73,7 +73,8 @@ typedef struct gtf_graph {
      * field of this struct, added after the others), then n_g8 nodes with <= 8 slots,
      * n_g16 with 9..16, n_g32 with 17..32, n_g64 with 33..64 (a group of that many lanes
      * per node), then n_big nodes with more slots (one thread per node). Built once per
-     * graph (gtf/device.py); a shard's graph view holds the schedule of its own receivers. */
+     * graph (gtf_graph_prepare, or gtf/device.py on the host); a shard's graph view holds the
+     * schedule of its own receivers. */
     const int32_t* sched;     /* [N] */
     int32_t n_g8;
     int32_t n_g16;
@@ -723,6 +724,63 @@ int gtf_build_event_csr(gtf_event_csr* ev);
  * (helper.py:465-521) and event_conversion.py:63-84 like the host builder. */
 size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows);
 int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* ---- graph preparation: the optional fields of gtf_graph, built on the GPU -----------
+ * The schedules and graph-static slot tables that the lane-group kernels read (every
+ * optional field of gtf_graph up to v8 except the packed schedule and the padded tiles),
+ * from the base fields alone -- array for array what gtf/device.py builds on the host
+ * (node_schedule, sched_segments, sender_schedule, sender_lanes, slot_classes,
+ * slot_static_words, slot_sender_xzr). No reference counterpart: the reference walks
+ * networkx dicts. gtf_prepare.hip.
+ *
+ * gtf_graph_tables: device pointers, caller-allocated at the sizes below (N, S, E =
+ * n_nodes, n_slots, n_edges); NULL = table not wanted. out_sched and out_lanes are
+ * capacities: the first 4 (n_o4 + n_o8 + n_o16) and 2 (4 n_o4 + 8 n_o8) words are written. */
+typedef struct gtf_graph_tables {
+    int32_t*  slot_dst;       /* [S]   receiver of each slot */
+    int32_t*  out_dst;        /* [E]   slot_dst[out_slot] */
+    double*   slot_layer;     /* [S]   layer[slot_src], NaN for an orphan key */
+    int32_t*  slot_outpos;    /* [S]   position in the sender's out-list, -1 = no edge */
+    int32_t*  slot_outidx;    /* [S]   global out-edge index, -1 = no edge */
+    uint64_t* slot_class;     /* [S]   written only with slot_sflags and slot_xclass */
+    uint8_t*  slot_sflags;    /* [S] */
+    uint64_t* slot_xclass;    /* [S] */
+    double*   slot_sxzr;      /* [3S]  gnn[slot_src][0, 2, 3], NaN rows for orphan keys */
+    uint32_t* slot_static;    /* [S]   needs the three class tables */
+    int32_t*  sched;          /* [N] */
+    int32_t*  sched_seg;      /* [2N]  needs sched */
+    int32_t*  out_sched;      /* [4N] capacity */
+    int32_t*  out_lanes;      /* [16N] capacity: 2 * 8 lanes * at most N senders; needs out_sched */
+} gtf_graph_tables;
+
+/* Bytes of device scratch gtf_graph_prepare needs (positive for an empty graph too). */
+size_t gtf_graph_prepare_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_edges);
+
+/* Reads only n_nodes, n_slots, n_edges, slot_ptr, slot_src, out_ptr, out_slot, is_edge,
+ * rev_edge, gnn and layer of *g; writes every table of *t that was asked for, on `stream`;
+ * stores each written table's pointer and the counts n_g2, n_g4, n_g6, n_g8, n_g12, n_g16,
+ * n_g32, n_g64, n_big, n_o4, n_o8, n_o16 in *g. The counts come back through one small
+ * device-to-host copy: the call SYNCHRONISES `stream` once (after the schedules; the slot
+ * and out-edge tables are still in flight on `stream` when it returns, so the workspace
+ * stays allocated until `stream` has run them). solo, xyzr,
+ * pack_ent / pack_wave, the padded-tile fields and every mutable struct stay the caller's.
+ *
+ * A table not asked for leaves its optional gtf_graph field NULL (slot_dst and slot_outpos,
+ * which gtf_pass requires, are then left as the caller set them), and the dependent fields
+ * follow: no sched -> sched_seg NULL and n_g* = n_big = 0; no out_sched -> out_lanes NULL
+ * and n_o* = 0; slot_class, slot_sflags and slot_xclass are written and set only when all
+ * three were asked for, else all three are NULL (the node kernel reads all three when it
+ * sees slot_xclass), and slot_static with them. The orders are the host builders': inside
+ * each schedule bucket the narrow sub-class first (<= 2, <= 6, <= 12 slots), ascending
+ * node index inside a class; class equality is floating-point == (-0.0 == 0.0; a NaN or an
+ * orphan key equals only itself).
+ *
+ * Status as gtf_pass: -3 for another ABI; -2 for negative sizes, a missing base array or a
+ * workspace below gtf_graph_prepare_workspace_bytes, all decided on the host before any
+ * launch. n_nodes == 0, or n_slots == n_edges == 0: returns 0 with zero counts and NULL
+ * tables, nothing launched (the kernels then take one thread per node). */
+int gtf_graph_prepare(gtf_graph* g, const gtf_graph_tables* t, void* workspace, size_t workspace_bytes,
+                      gtf_stream_t stream);
 
 /* Member order of every extraction candidate as the reference builds it: CCA over the
  * active edges of each subgraph (extract_track_candidates.py:332-346) -- networkx
