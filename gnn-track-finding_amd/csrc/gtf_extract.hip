@@ -540,8 +540,9 @@ int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_ext
         hipLaunchKernelGGL(k_ex_inactive, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, io->sub_id,
                            w.inactive);
     // hook + compress until no root changes (candidates are short: a few rounds)
+    int32_t changed = 0;
     for (int round = 0; round < 64; round++) {
-        int32_t zero = 0, changed = 0;
+        int32_t zero = 0;
         if (hipMemcpyAsync(w.flag, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
         if (g->n_slots > 0)
             hipLaunchKernelGGL(k_ex_hook, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, io->label, w.flag);
@@ -553,6 +554,7 @@ int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_ext
         }
         if (!changed) break;
     }
+    if (changed) { gtf::set_error("gtf_extract_candidates: CCA did not converge"); return -1; }
     hipLaunchKernelGGL(k_ex_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, io->sub_id, io->sub_ptr, w.inactive,
                        io->order_key, io->label, w.keys_in, w.vals_in);
     size_t cb = w.cub_bytes;

@@ -572,7 +572,8 @@ typedef struct gtf_extract_io {
 } gtf_extract_io;
 
 size_t gtf_extract_workspace_bytes(int32_t n_nodes, int32_t n_sub);
-/* synchronises the stream once per connected-components round (a few rounds) */
+/* synchronises the stream once per connected-components round (a few rounds); -1 with
+ * "CCA did not converge" when none of 64 rounds passed without a change */
 int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_extract_io* io,
                            const gtf_extract_params* p, void* workspace, gtf_stream_t stream);
 

@@ -894,7 +894,7 @@ def _kf_step(x, P, F, Q, H, R, z):
     return x, P
 
 
-def kf_track_fit_moliere(sigma0xy, sigma0rz, coords, endcap_boundary):         # :209-327
+def kf_track_fit_moliere(sigma0xy, sigma0rz, coords, endcap_boundary, chi2=None):   # :209-327
     from scipy.stats import distributions
     f_x = np.array([coords[0][1], 0., 0.])
     f_P = np.array([[sigma0xy**2, 0., 0.], [0., 1., 0.], [0., 0., 1.]])
@@ -945,7 +945,10 @@ def kf_track_fit_moliere(sigma0xy, sigma0rz, coords, endcap_boundary):         #
         S = g_H.dot(g_P).dot(g_H.T) + g_R
         c2zr.append(res.T.dot(np.linalg.inv(S)).dot(res))
     dof = len(coords) - 2
-    return (float(distributions.chi2.sf(sum(c2xy), dof)), float(distributions.chi2.sf(sum(c2zr), dof)))
+    pv, pz = float(distributions.chi2.sf(sum(c2xy), dof)), float(distributions.chi2.sf(sum(c2zr), dof))
+    if chi2 is not None:                       # the two chi-square sums, for the caller's record
+        chi2[:] = [float(np.ravel(sum(c2xy))[0]), float(np.ravel(sum(c2zr))[0])]
+    return pv, pz
 
 
 def extract_candidates(g: TrackGraph, vivl, p_accept, fragment, separation, merge_threshold, sigma0xy,
@@ -974,8 +977,10 @@ def extract_candidates(g: TrackGraph, vivl, p_accept, fragment, separation, merg
             continue
         coords = sorted([ac[v] for v in an], key=lambda c: c[3], reverse=True)
         coords = rotate_track(coords, separation)
-        pv, pz = kf_track_fit_moliere(sigma0xy, sigma0rz, coords, endcap_boundary)
+        c2 = [np.nan, np.nan]
+        pv, pz = kf_track_fit_moliere(sigma0xy, sigma0rz, coords, endcap_boundary, c2)
         rec["pval_xy"], rec["pval_zr"] = pv, pz
+        rec["chi2_xy"], rec["chi2_zr"] = c2
         if pv >= p_accept and pz >= p_accept:
             rec["status"] = "extracted"
             extracted.append(np.asarray(nodes))
