@@ -47,6 +47,25 @@ class GtfGraphTables(ctypes.Structure):
                 ("sched", P), ("sched_seg", P), ("out_sched", P), ("out_lanes", P)]
 
 
+class GtfSubsetCounts(ctypes.Structure):
+    """gtf_subset_counts: the sizes gtf_graph_subset_plan found for the result"""
+    _fields_ = [("n_nodes", I32), ("n_slots", I32), ("n_edges", I32), ("n_sub", I32)]
+
+
+class GtfSubsetOut(ctypes.Structure):
+    """gtf_subset_out: the caller-allocated outputs of gtf_graph_subset_apply (NULL = not wanted)"""
+    _fields_ = [("node_map", P), ("slot_map", P), ("slot_ptr", P), ("slot_src", P), ("out_ptr", P),
+                ("out_slot", P), ("sub_id", P), ("solo", P)]
+
+
+class GtfColumn(ctypes.Structure):
+    """gtf_column: one column of gtf_subset_gather"""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", I32), ("fill", I32)]
+
+
+COL_COPY, COL_ZERO_ORPHAN, COL_NAN_ORPHAN, COL_ZERO_ALL = 0, 1, 2, 3   # GTF_COL_*
+
+
 class GtfNodes(ctypes.Structure):
     _fields_ = [("has_merged", P), ("merged_state", P), ("merged_cov", P), ("merged_prior", P),
                 ("has_tse", P), ("has_uts", P), ("degree", P)]
@@ -163,6 +182,8 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
+           "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
+           "gtf_subset_gather", "gtf_refresh_send_mw",
            "gtf_updated_state_pair_counts", "gtf_updated_state_distances", "gtf_set_diagnostics",
            "gtf_device_init", "gtf_malloc", "gtf_free", "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod",
            "gtf_memset", "gtf_stream_synchronize",
@@ -250,6 +271,12 @@ def lib(lean: bool = False):
     L.gtf_graph_prepare_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_graph_prepare_workspace_bytes.argtypes = [I32, I32, I32]
     L.gtf_graph_prepare.argtypes = [G, ctypes.POINTER(GtfGraphTables), P, ctypes.c_size_t, P]
+    L.gtf_graph_subset_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_graph_subset_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.gtf_graph_subset_plan.argtypes = [G, P, P, P, I32, P, P, ctypes.c_size_t, ctypes.POINTER(GtfSubsetCounts), P]
+    L.gtf_graph_subset_apply.argtypes = [G, P, ctypes.POINTER(GtfSubsetOut), P]
+    L.gtf_subset_gather.argtypes = [P, I32, ctypes.POINTER(GtfColumn), I32, P]
+    L.gtf_refresh_send_mw.argtypes = [G, P, P, P, P]
     L.gtf_candidate_order.argtypes = [ctypes.POINTER(GtfCandidateGraph), P]
     L.gtf_updated_state_pair_counts.argtypes = [G, N, S, E, P, P]
     L.gtf_updated_state_distances.argtypes = [G, N, S, E, P, P, ctypes.POINTER(GtfPairOut), P]
@@ -285,7 +312,8 @@ def lib(lean: bool = False):
                "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod", "gtf_memset", "gtf_stream_synchronize",
                "gtf_comm_unique_id", "gtf_comm_init", "gtf_comm_destroy", "gtf_comm_rank", "gtf_comm_size",
                "gtf_halo_exchange", "gtf_halo_alltoall", "gtf_allreduce_max_i64", "gtf_allgather_bytes",
-               "gtf_tag_propagate_shard", "gtf_graph_prepare"):
+               "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
+               "gtf_subset_gather", "gtf_refresh_send_mw"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -293,6 +293,13 @@ class DeviceGraph:
             self._device_tables(g, classes, schedule)
             self._finish(g, pack)
             return
+        self._host_tables(g, classes, schedule, pack)
+        self._upload_rest(g, pack)
+        self._finish(g, pack)
+
+    def _host_tables(self, g: TrackGraph, classes, schedule, pack):
+        """tables "host": the schedules and slot tables from the NumPy builders of this module"""
+        up = self._up
         up("slot_dst", g.slot_dst().astype(np.int32))
         out_dst = g.slot_dst()[g.out_slot].astype(np.int32) if g.n_edges else np.zeros(0, np.int32)
         up("out_dst", out_dst)
@@ -357,8 +364,6 @@ class DeviceGraph:
             self.n_pack_waves = int(pwave.size - 1)
         self.n_g = self.n_g_all if schedule else [0] * len(BUCKETS)
         self.use_sched = schedule
-        self._upload_rest(g, pack)
-        self._finish(g, pack)
 
     def _upload_rest(self, g: TrackGraph, pack):
         """solo and the node and slot arrays of the graph (no schedule, no slot table)"""
@@ -371,6 +376,11 @@ class DeviceGraph:
             else:
                 solo = np.zeros(0, np.uint8)
             up("solo", solo)
+        # the subgraph ids, for subset(): every value in [0, n_sub)
+        sub = g.node["sub_id"].astype(np.int32)
+        self.n_sub = max(int(g.n_subgraphs), int(sub.max()) + 1 if sub.size else 0, 0)
+        self._sub_ok = not sub.size or int(sub.min()) >= 0
+        up("sub_id", sub)
         for f in ("gnn", "xyzr", "layer") + MUTABLE_NODE:
             up(f, g.node[f])
         for f in SLOT_FIELDS:
@@ -830,6 +840,150 @@ class DeviceGraph:
             else:
                 g.slot[f][self.slot_perm[sm]] = a[sm]
         return g
+
+    # ------------------------------------------------ node removal between iterations
+    SUBSET_FILL = {"is_edge": nat.COL_ZERO_ORPHAN, "rev_edge": nat.COL_ZERO_ORPHAN, "act": nat.COL_ZERO_ORPHAN,
+                   "edge_mw": nat.COL_NAN_ORPHAN, "send_mw": nat.COL_NAN_ORPHAN, "uts_fresh": nat.COL_ZERO_ALL}
+
+    def _base_graph(self):
+        """a gtf_graph of the base fields alone (what plan, apply and prepare read)"""
+        p = self.ptr
+        return nat.GtfGraph(n_nodes=self.n_nodes, n_slots=self.n_slots, n_edges=self.n_edges, slot_ptr=p("slot_ptr"),
+                            slot_src=p("slot_src"), out_ptr=p("out_ptr"), out_slot=p("out_slot"),
+                            is_edge=p("is_edge"), rev_edge=p("rev_edge"), gnn=p("gnn"), layer=p("layer"))
+
+    def _as_dev(self, a, dtype, n, what):
+        """`a` (a host array, or a device array of this graph's allocator) as a flat device array
+        of n elements of dtype"""
+        dtype = np.dtype(dtype)
+        if self.torch is not None and self.torch.is_tensor(a):
+            t = a.to(device=self.device, dtype=getattr(self.torch, dtype.name)).contiguous().reshape(-1)
+        elif hasattr(a, "data_ptr"):   # a gtf.devmem array
+            if a.dtype != dtype:
+                raise ValueError("%s: a device array must be %s" % (what, dtype.name))
+            t = a
+        else:
+            t = self._dev_from(np.ascontiguousarray(np.asarray(a), dtype=dtype))
+        if t.numel() != n:
+            raise ValueError("%s must have %d elements" % (what, n))
+        return t
+
+    def subset(self, keep, gnn=None) -> "DeviceGraph":
+        """The graph after removing the nodes whose `keep` is false, built on the device:
+        gtf.graph.subset (extract_track_candidates.py:459-467), array for array, by
+        gtf_graph_subset_plan / _apply and gtf_subset_gather, with the child's schedules and
+        slot tables by gtf_graph_prepare (tables == "device" whatever this graph had).
+        keep: host bool [N] or device uint8 [N] in this graph's node order; gnn: optional
+        [N, 4] replacement of the GNN coordinates (host or device) -- the extraction's
+        close-proximity merge. The child's uts_fresh is 0 in both bits: its entries read
+        their stored xyzr until the next message passing rewrites them. Natural layout only."""
+        if self.layout != "natural" or self.n_pack_waves:
+            raise NotImplementedError("DeviceGraph.subset: only layout='natural' without pack=True (the renumbered, "
+                                      "padded and packed layouts are not carried over); this graph has layout=%r, "
+                                      "pack=%r" % (self.layout, bool(self.n_pack_waves)))
+        if not self._sub_ok:
+            raise ValueError("DeviceGraph.subset needs sub_id >= 0 on every node")
+        N, S, E = self.n_nodes, self.n_slots, self.n_edges
+        if not (self.torch is not None and self.torch.is_tensor(keep)) and not hasattr(keep, "data_ptr"):
+            keep = np.asarray(keep)
+            if keep.shape != (N,):
+                raise ValueError("keep must be a mask over the %d nodes" % N)
+            keep = (keep != 0).astype(np.uint8)
+        keep_t = self._as_dev(keep, np.uint8, N, "keep")
+        gnn_t = self._as_dev(gnn, np.float64, 4 * N, "gnn") if gnn is not None else self.t["gnn"]
+        self.materialize()
+        L, vp = self.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
+        cg = self._base_graph()
+        nb = int(L.gtf_graph_subset_workspace_bytes(N, S, E, self.n_sub))
+        ws = self._dev_empty(nb, np.uint8)
+        cnt = nat.GtfSubsetCounts()
+        nat.check(L.gtf_graph_subset_plan(ctypes.byref(cg), self.ptr("tse_rank"), self.ptr("uts_rank"),
+                                          self.ptr("sub_id"), self.n_sub, vp(keep_t), vp(ws), ctypes.c_size_t(nb),
+                                          ctypes.byref(cnt), self.stream))
+        N2, S2, E2 = cnt.n_nodes, cnt.n_slots, cnt.n_edges
+        c = DeviceGraph.__new__(DeviceGraph)
+        c.mem, c.torch, c.lib, c.device = self.mem, self.torch, self.lib, self.device
+        c.layout, c.order, c.slot_perm, c.pad_plan = "natural", None, None, None
+        c.slot_ptr_host = None
+        c.n_nodes, c.n_slots, c.n_edges, c.n_sub, c._sub_ok = N2, S2, E2, cnt.n_sub, True
+        c.tables = "device"
+        c.t = {}
+        struct = [("node_map", N2, np.int32), ("slot_map", S2, np.int32), ("slot_ptr", N2 + 1, np.int32),
+                  ("slot_src", S2, np.int32), ("out_ptr", N2 + 1, np.int32), ("out_slot", E2, np.int32),
+                  ("sub_id", N2, np.int32), ("solo", N2, np.uint8)]
+        for name, n, dt in struct:
+            c.t[name] = c._dev_empty(n, dt) if N else c._dev_zeros(n, dt)
+        if N:
+            so = nat.GtfSubsetOut(**{name: c.ptr(name) for name, _, _ in struct})
+            nat.check(L.gtf_graph_subset_apply(ctypes.byref(cg), vp(ws), ctypes.byref(so), self.stream))
+        # the payload: every device-resident node and slot array through the maps
+        for axis, rows, names in ((0, N2, ("gnn", "xyzr", "layer") + MUTABLE_NODE),
+                                  (1, S2, tuple(f for f in SLOT_FIELDS if f not in ("slot_key", "slot_src")))):
+            cols = []
+            for f in names:
+                src = gnn_t if f == "gnn" else self.t[f]
+                dt, shape, _ = (NODE_FIELDS if axis == 0 else SLOT_FIELDS)[f]
+                width = int(np.prod(shape, dtype=np.int64))
+                c.t[f] = c._dev_empty(rows * width, dt)
+                if rows:
+                    cols.append(nat.GtfColumn(vp(src), c.ptr(f), width * np.dtype(dt).itemsize,
+                                              self.SUBSET_FILL.get(f, nat.COL_COPY) if axis else nat.COL_COPY))
+            if cols:
+                arr = (nat.GtfColumn * len(cols))(*cols)
+                nat.check(L.gtf_subset_gather(vp(ws), axis, arr, len(cols), self.stream))
+        # the plan's workspace and a converted keep / gnn go out of scope with kernels in flight: a
+        # torch allocation is reused in stream order, a plain one is freed at once
+        if self.torch is None:
+            nat.check(L.gtf_stream_synchronize(None))
+        shape = TrackGraph(N2, S2, None, None, np.zeros(E2, np.int32), {}, {}, cnt.n_sub)   # (sizes only)
+        if N2 > 0 and (S2 > 0 or E2 > 0):
+            c._device_tables(shape, None, True)
+        else:   # nothing for gtf_graph_prepare to build: the few tables of a slot-free graph from the host
+            from .graph import empty_arrays
+            z = np.zeros(N2 + 1, np.int32)
+            solo = c.t["solo"]
+            c._host_tables(TrackGraph(N2, 0, z, z, np.zeros(0, np.int32), empty_arrays(NODE_FIELDS, N2),
+                                      empty_arrays(SLOT_FIELDS, 0), cnt.n_sub), None, True, False)
+            c.t["solo"] = solo
+        c._finish(shape, False)
+        return c
+
+    def refresh_send_mw(self):
+        """gtf.graph.refresh_send_mw on the device (gtf_refresh_send_mw): send_mw of every edge
+        from the sender's current tse_mw, NaN where the sender holds no such entry"""
+        self._natural_only("refresh_send_mw")
+        nat.check(self.lib.gtf_refresh_send_mw(ctypes.byref(self.cg_sched), self.ptr("tse_rank"), self.ptr("tse_mw"),
+                                               self.ptr("send_mw"), self.stream))
+
+    def to_host(self, parent: TrackGraph) -> TrackGraph:
+        """A subset() child as a host graph: the structure and every device-resident field
+        downloaded, the host-only fields (slot_key, node_id, tag) taken from `parent` -- the host
+        graph of the DeviceGraph that subset() was called on -- through node_map / slot_map."""
+        if "node_map" not in self.t:
+            raise ValueError("to_host: only a graph made by DeviceGraph.subset() has the maps to its parent")
+        self.materialize()
+        N, S = self.n_nodes, self.n_slots
+        nm = self._np(self.t["node_map"]).astype(np.int64)
+        sm = self._np(self.t["slot_map"]).astype(np.int64)
+        if (N and nm.max() >= parent.n_nodes) or (S and sm.max() >= parent.n_slots):
+            raise ValueError("to_host: `parent` is not the graph this one was cut from")
+        node, slot = {}, {}
+        for f, (dt, shape, _) in NODE_FIELDS.items():
+            if f in self.t:
+                node[f] = self._np(self.t[f]).reshape((N,) + shape).astype(dt, copy=False)
+            else:
+                node[f] = parent.node[f][nm].copy()
+        for f, (dt, shape, _) in SLOT_FIELDS.items():
+            if f in self.t:
+                slot[f] = self._np(self.t[f]).reshape((S,) + shape).astype(dt, copy=False)
+            else:
+                slot[f] = parent.slot[f][sm].copy()
+        slot["uts_fresh"] = slot["uts_fresh"] & 1   # (bit 1 is cleared by materialize())
+        from .graph import check_layout
+        h = TrackGraph(N, S, self._np(self.t["slot_ptr"]), self._np(self.t["out_ptr"]), self._np(self.t["out_slot"]),
+                       node, slot, self.n_sub)
+        check_layout(h)
+        return h
 
     def _natural_only(self, what):
         """node-indexed arrays cross these methods in host order: every layout whose node order

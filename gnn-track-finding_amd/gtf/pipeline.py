@@ -14,7 +14,9 @@ activation mask in place), and the host only builds the next iteration's graph f
 the extraction's verdict (:func:`gtf.graph.subset`, the packed form of
 ``remove_nodes_from`` + dropping fragments) with the extraction's GNN_Measurement
 coordinate mutation (close-proximity merging, extract_track_candidates.py:91-118)
-carried over.
+carried over -- or, with ``run(..., resident=True)``, the device does
+(:meth:`gtf.device.DeviceGraph.subset`) and the graph stays in HBM from one iteration
+to the next.
 
 Event conversion (:func:`build_event`, event_conversion.py:53-101): the packed graph
 and its orders come from gtf_build_event_csr (csrc/gtf_build.cpp: the reference's
@@ -112,12 +114,22 @@ def _ids(g: TrackGraph, groups):
 
 
 def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
-        device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host") -> List[Iteration]:
+        device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host",
+        resident: bool = False) -> List[Iteration]:
     """Iterations ``first`` .. ``first + iterations - 1`` of the loop, starting from
     the stage input ``g`` (the event network for iteration 1). Stops early when
     nothing remains. keep_graphs: also return each iteration's stage output and
     remaining graphs (for saving, gtf.store). tables: passed to every DeviceGraph ("device":
-    the schedules and slot tables by gtf_graph_prepare instead of the host builders)."""
+    the schedules and slot tables by gtf_graph_prepare instead of the host builders).
+    resident: the next iteration's graph is cut on the device -- DeviceGraph.subset(keep,
+    gnn=merged coordinates) and refresh_send_mw() (gtf_graph_subset_plan / _apply,
+    gtf_subset_gather, gtf_refresh_send_mw) instead of graph.subset + refresh_send_mw on the
+    host and a fresh upload; an even iteration's update() runs on that object, and the next
+    iteration's stage reuses it. The candidate order and the stage outputs
+    (extract.candidate_order, extract.outputs) stay on the host, so the download after every
+    stage stays, and the next iteration's host graph is the child's to_host(): what this mode
+    removes is the host subset, the host refresh, the re-upload and the second DeviceGraph of
+    even iterations. Same results, array for array."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
@@ -126,11 +138,13 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
         raise ValueError("vivl must have one row per node")
     out = []
     torch = None
+    dnext = None   # resident: the DeviceGraph that already holds the iteration's input
     for it in range(first, first + iterations):
         if g.n_nodes == 0:
             break
         t0 = time.perf_counter()
-        d = DeviceGraph(g, device, tables=tables)
+        d = dnext if dnext is not None else DeviceGraph(g, device, tables=tables)
+        dnext = None
         torch = d.torch
         d.clear_errors()
         if it == 1:
@@ -155,9 +169,18 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
         for r in o["remaining"]:
             keep[r] = True
         g.node["gnn"] = res["gnn"]                 # GNN_Measurement mutated in place by merging
-        nxt = subset(g, keep)
-        refresh_send_mw(nxt)
-        if it % 2 == 0 and nxt.n_nodes:
+        if resident:
+            dnext = d.subset(keep, gnn=res["gnn"])
+            dnext.refresh_send_mw()
+            if it % 2 == 0 and dnext.n_nodes:      # remove_state_metadata.py, as below
+                dnext.clear_errors()
+                dnext.update(p)
+                dnext.raise_errors()
+            nxt = dnext.to_host(g)
+        else:
+            nxt = subset(g, keep)
+            refresh_send_mw(nxt)
+        if not resident and it % 2 == 0 and nxt.n_nodes:
             # remove_state_metadata.py on the remaining directory (run_gnn_trackml_mod.sh:137-139)
             du = DeviceGraph(nxt, device, tables=tables)
             du.clear_errors()

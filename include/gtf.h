@@ -783,6 +783,102 @@ size_t gtf_graph_prepare_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32
 int gtf_graph_prepare(gtf_graph* g, const gtf_graph_tables* t, void* workspace, size_t workspace_bytes,
                       gtf_stream_t stream);
 
+/* ---- node removal between two iterations, on the GPU ----------------------------------
+ * The packed form of the reference's subGraph.remove_nodes_from(extracted)
+ * (extract_track_candidates.py:459-467) followed by dropping the emptied subgraphs: array
+ * for array gtf/graph.py's subset() -- kept nodes in order; inside a kept receiver the
+ * slots whose sender is kept (an edge or a key of either state dict) in their old order,
+ * then the removed senders' surviving dict keys as orphans (slot_src -1, no edge) in the
+ * order pack() discovers them: by tse_rank where it is >= 0, then the uts_rank-only keys by
+ * uts_rank, ties by old slot index; edge-only slots of removed senders vanish; the out view
+ * keeps its successor order; sub_id is renumbered densely. gtf_subset.hip.
+ *
+ * Three steps, because the sizes of the result are known only after the mask is counted:
+ * plan (counts them, SYNCHRONISES once), then the caller allocates, then apply (structure)
+ * and gather (payload), neither of which synchronises. Every step reads the plan from the
+ * same caller-owned workspace. */
+typedef struct gtf_subset_counts {
+    int32_t n_nodes, n_slots, n_edges, n_sub;   /* of the result */
+} gtf_subset_counts;
+
+/* Device pointers, caller-allocated at the planned sizes (N2, S2, E2 = the counts);
+ * NULL = array not wanted. */
+typedef struct gtf_subset_out {
+    int32_t* node_map;   /* [N2]   old node index of each new node */
+    int32_t* slot_map;   /* [S2]   old slot index of each new slot */
+    int32_t* slot_ptr;   /* [N2+1] new receiver segments */
+    int32_t* slot_src;   /* [S2]   new sender index, -1 for an orphan */
+    int32_t* out_ptr;    /* [N2+1] new out view */
+    int32_t* out_slot;   /* [E2]   new slot of each surviving out-edge, successor order */
+    int32_t* sub_id;     /* [N2]   rank of the old id among the ids that keep a node */
+    uint8_t* solo;       /* [N2]   1 = the only kept node of its subgraph */
+} gtf_subset_out;
+
+/* How gtf_subset_gather fills the rows of a column (an orphan: new slot_src == -1; the
+ * orphan kinds are plain copies on the node axis). */
+#define GTF_COL_COPY        0   /* dst row = src row of the old node / slot */
+#define GTF_COL_ZERO_ORPHAN 1   /* ... an orphan's row zeroed (is_edge, rev_edge, act) */
+#define GTF_COL_NAN_ORPHAN  2   /* ... an orphan's row 8-byte NaNs (edge_mw, send_mw); row_bytes % 8 == 0 */
+#define GTF_COL_ZERO_ALL    3   /* every row zeroed, src not read (uts_fresh) */
+
+typedef struct gtf_column {
+    const void* src;     /* device: [old rows] of row_bytes each (may be NULL with GTF_COL_ZERO_ALL) */
+    void* dst;           /* device: [new rows] of row_bytes each */
+    int32_t row_bytes;   /* >= 1 */
+    int32_t fill;        /* GTF_COL_* */
+} gtf_column;
+
+/* Bytes of device scratch for a subset of a graph of these sizes whose sub_id values lie
+ * in [0, n_sub) (extract_track_candidates.py:459-467; gtf/graph.py subset). Positive for an
+ * empty graph, non-decreasing in every argument (negative arguments count as 0). */
+size_t gtf_graph_subset_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_edges, int32_t n_sub);
+
+/* Plan (extract_track_candidates.py:459-467; gtf/graph.py subset): reads only n_nodes,
+ * n_slots, n_edges, slot_ptr, slot_src, out_ptr, out_slot and is_edge of *g (no optional
+ * table), tse_rank / uts_rank [S], sub_id [N] (values in [0, n_sub), any order; a value
+ * outside joins no subgraph count) and keep [N] (nonzero = kept), all device arrays.
+ * Leaves the old -> new and new -> old node and slot maps, the per-node slot and out-edge
+ * offsets and the renumbered sub_id / solo in `workspace`, and the sizes of the result in
+ * the host struct *counts, through one small device-to-host copy: the call SYNCHRONISES
+ * `stream` once (as gtf_graph_prepare). The workspace is then what gtf_graph_subset_apply
+ * and gtf_subset_gather read; it stays the caller's until `stream` has run them.
+ * Status: -3 for another ABI; -2 for negative sizes, a missing array (the message names
+ * it), slots or edges without nodes, or a workspace below
+ * gtf_graph_subset_workspace_bytes, all decided on the host before any launch.
+ * n_nodes == 0: returns 0 with zero counts, nothing launched (apply and gather on such a
+ * plan must not be called: there is nothing to write). */
+int gtf_graph_subset_plan(const gtf_graph* g, const int32_t* tse_rank, const int32_t* uts_rank,
+                          const int32_t* sub_id, int32_t n_sub, const uint8_t* keep, void* workspace,
+                          size_t workspace_bytes, gtf_subset_counts* counts, gtf_stream_t stream);
+
+/* Apply (extract_track_candidates.py:459-467; gtf/graph.py subset): writes the wanted
+ * structure arrays of *out from the plan in `workspace` (*g the graph that was planned).
+ * Does not synchronise. Status as the plan (-3 / -2 on the host). */
+int gtf_graph_subset_apply(const gtf_graph* g, const void* workspace, const gtf_subset_out* out,
+                           gtf_stream_t stream);
+
+/* Payload gather (the row copies of gtf/graph.py subset; extract_track_candidates.py:459-467
+ * keeps the attribute dicts of the nodes that stay): for every column, new row i = old row
+ * node_map[i] (axis 0) or slot_map[i] (axis 1) of the plan in `workspace`, filled as
+ * `fill` says. `cols` is a HOST array; the column table travels in the kernel arguments,
+ * many columns per launch. Rows that are multiples of 8 bytes (with 8-byte aligned
+ * pointers) move as 8-byte words, of 4 as 4-byte words. Any row_bytes >= 1; a caller's own
+ * per-node or per-slot arrays ride along. Does not synchronise. n_cols == 0: returns 0.
+ * -2: axis not 0 / 1, row_bytes <= 0, an unknown fill, a NULL dst or (unless
+ * GTF_COL_ZERO_ALL) src, GTF_COL_NAN_ORPHAN on rows that are no multiple of 8 bytes. */
+int gtf_subset_gather(const void* workspace, int32_t axis, const gtf_column* cols, int32_t n_cols,
+                      gtf_stream_t stream);
+
+/* gtf/graph.py refresh_send_mw (the value pack() stores; used after subset(),
+ * extract_track_candidates.py:459-467, and by event conversion): for every slot k that is
+ * an edge u -> v, send_mw[k] = tse_mw of the slot (receiver u, sender v) when that slot
+ * exists and has tse_rank >= 0, else NaN; NaN for every slot that is no edge. Reads
+ * n_nodes, n_slots, slot_ptr, slot_src, is_edge (and slot_dst when set) of *g. Relies on the
+ * layout invariant that a receiver's non-orphan slots ascend by slot_src (orphans last): a
+ * binary search in u's segment. send_mw may not alias tse_mw. Does not synchronise. */
+int gtf_refresh_send_mw(const gtf_graph* g, const int32_t* tse_rank, const double* tse_mw, double* send_mw,
+                        gtf_stream_t stream);
+
 /* Member order of every extraction candidate as the reference builds it: CCA over the
  * active edges of each subgraph (extract_track_candidates.py:332-346) -- networkx
  * weakly connected components, each copied as subGraph.subgraph(component) (set order
