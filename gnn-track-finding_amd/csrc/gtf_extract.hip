@@ -13,6 +13,16 @@
 //     rotate_track (:176-195), the xy (3-state OU) and rz (2-state) Kalman fits with
 //     filterpy 1.4.5 predict/update (:209-327) and the chi-square p-values
 //     (scipy.stats.chi2.sf = the regularized upper incomplete gamma, cephes igamc).
+//
+// Around it, for a loop that stays in HBM (gtf.pipeline.run(resident="device")):
+//  * gtf_candidate_order_device: the member order of step 2 as the reference builds it
+//    (:332-346; gtf_candidate_order in gtf_build.cpp is the host form) -- the same hook +
+//    compress rounds over the edges with act != 0, one sort for the members, ranks for
+//    components of at least half their subgraph, one thread's BFS into a CPython set
+//    (gtf_pyset.h) for the smaller ones;
+//  * gtf_extract_outputs: the keep mask and the extracted / remaining / fragment lists
+//    (:423-430, :459-467; gtf/extract.py outputs) by exclusive sums over the results and over
+//    the sorted member list that step 2 left in the workspace.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -20,6 +30,7 @@
 
 #include "../../include/gtf.h"
 #include "gtf_math.h"
+#include "gtf_pyset.h"
 
 namespace gtf {
 void set_error(const char* msg);
@@ -55,10 +66,12 @@ __device__ __forceinline__ int find_root(const int32_t* label, int x) {
     return x;
 }
 
-// hook the larger root under the smaller one for every active edge
+// hook the larger root under the smaller one for every active edge (ANY: act != 0, the
+// candidate order's rule -- gtf_candidate_order walks those; else act == 1, the extraction's)
+template <bool ANY>
 __global__ void __launch_bounds__(BLOCK) k_ex_hook(gtf_graph g, gtf_edges e, int32_t* label, int32_t* flag) {
     const int k = blockIdx.x * BLOCK + threadIdx.x;
-    if (k >= g.n_slots || !g.is_edge[k] || e.act[k] != 1) return;
+    if (k >= g.n_slots || !g.is_edge[k] || (ANY ? e.act[k] == 0 : e.act[k] != 1)) return;
     const int u = g.slot_src[k], v = g.slot_dst[k];
     const int ru = find_root(label, u), rv = find_root(label, v);
     if (ru == rv) return;
@@ -476,6 +489,35 @@ __global__ void __launch_bounds__(BLOCK) k_ex_flags(int n, gtf_extract_io io) {
     if (v < n) io.extracted[v] = io.status[io.label[v]] == EX_EXTRACTED ? 1 : 0;
 }
 
+// label[v] = v, the subgraphs' inactive flags, then hook + compress until no root changes
+// (candidates are short: a few rounds; one stream synchronisation per round): every
+// component ends labelled by its minimum node index. 0, or -1 with the error set.
+template <bool ANY>
+int cca_rounds(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id, int n_sub, int32_t* label,
+               uint8_t* inactive, int32_t* flag, hipStream_t st, const char* fail, const char* stuck) {
+    const int n = g->n_nodes;
+    const int nb = grid(n > n_sub ? n : n_sub);
+    hipLaunchKernelGGL(k_ex_init, dim3(nb), dim3(BLOCK), 0, st, n, n_sub, label, inactive, flag);
+    if (g->n_slots > 0)
+        hipLaunchKernelGGL(k_ex_inactive, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, sub_id, inactive);
+    int32_t changed = 0;
+    for (int round = 0; round < 64; round++) {
+        int32_t zero = 0;
+        if (hipMemcpyAsync(flag, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        if (g->n_slots > 0)
+            hipLaunchKernelGGL(k_ex_hook<ANY>, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, label, flag);
+        hipLaunchKernelGGL(k_ex_compress, dim3(grid(n)), dim3(BLOCK), 0, st, n, label);
+        if (hipMemcpyAsync(&changed, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            gtf::set_error(fail);
+            return -1;
+        }
+        if (!changed) break;
+    }
+    if (changed) { gtf::set_error(stuck); return -1; }
+    return 0;
+}
+
 struct ExWs {
     uint64_t *keys_in, *keys_out;
     int32_t *vals_in, *vals_out, *is_start, *cidx, *cand_ptr, *flag;
@@ -511,9 +553,478 @@ ExWs carve_ex(void* base, int n, int n_sub) {
     return w;
 }
 
+// ------------------------------------------------------------------ sub_ptr
+// sub_id must read 0, 1, 2, ... grouped: each first node of a subgraph writes its pointer;
+// err is sub_ptr[n_sub], preset to N and overwritten only by a violation
+__global__ void __launch_bounds__(BLOCK) k_sub_ptr(int n, int n_sub, const int32_t* sub, int32_t* sub_ptr,
+                                                   int32_t* err) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const int s = sub[v], before = v ? sub[v - 1] : -1;
+    if (s < 0 || s >= n_sub || (s != before && s != before + 1) || (v == n - 1 && s != n_sub - 1)) {
+        *err = -1;         // (every writer stores the same value)
+        return;
+    }
+    if (s != before) sub_ptr[s] = v;
+}
+
+// ------------------------------------------------------------------ candidate order
+constexpr int32_t OERR_RANGE = 1, OERR_DUP = 2, OERR_OVER = 4;
+enum { OS_ERR = 0, OS_NCOMP = 1, OS_NSET = 2, OS_MAXSET = 3, OS_WORDS = 4 };
+
+__global__ void __launch_bounds__(BLOCK) k_ord_keys(int n, const int32_t* label, uint64_t* keys, int32_t* vals,
+                                                    uint8_t* seen) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= n) return;
+    keys[v] = ((uint64_t)(uint32_t)label[v] << 32) | (uint32_t)v;
+    vals[v] = v;
+    seen[v] = 0;
+}
+
+// the sorted ids: range (a negative id is a huge unsigned one) and duplicates
+__global__ void __launch_bounds__(BLOCK) k_ord_check_ids(int n, const uint64_t* ids, int32_t* err) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, OERR_RANGE);      // (only on a violation)
+    if (i > 0 && ids[i] == ids[i - 1]) atomicOr(err, OERR_DUP);
+}
+
+// is component c (< n_comp) ordered by the set walk? its subgraph has an inactive edge and
+// it holds fewer than half the subgraph's nodes
+__device__ __forceinline__ bool set_ordered(int c, const int32_t* cptr, const int32_t* memb, const int32_t* sub,
+                                            const int32_t* sub_ptr, const uint8_t* inactive) {
+    const int s = sub[memb[cptr[c]]];
+    return inactive[s] && 2 * (int64_t)(cptr[c + 1] - cptr[c]) < (int64_t)(sub_ptr[s + 1] - sub_ptr[s]);
+}
+
+// per component slot c in [0, n]: the words of its three set tables (0 when it is not
+// set-ordered or c >= n_comp), the flag and the size for the counts
+__global__ void __launch_bounds__(BLOCK) k_ord_words(int n, const int32_t* n_comp, const int32_t* cptr,
+                                                     const int32_t* memb, const int32_t* sub,
+                                                     const int32_t* sub_ptr, const uint8_t* inactive,
+                                                     int64_t* words, int32_t* so_flag, int32_t* so_size) {
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c > n) return;
+    const bool so = c < *n_comp && set_ordered(c, cptr, memb, sub, sub_ptr, inactive);
+    const int sz = so ? cptr[c + 1] - cptr[c] : 0;
+    words[c] = so ? 3 * set_capacity(sz) : 0;
+    if (c < n) {
+        so_flag[c] = so ? 1 : 0;
+        so_size[c] = sz;
+    }
+}
+
+// every node by its position i in the sorted member list: the whole subgraph's node order,
+// or the rank among the component's members; set-ordered components are left to k_ord_walk
+__global__ void __launch_bounds__(BLOCK) k_ord_rank(int n, const int32_t* memb, const int32_t* is_start,
+                                                    const int32_t* cidx, const int32_t* cptr, const int32_t* sub,
+                                                    const int32_t* sub_ptr, const uint8_t* inactive,
+                                                    int32_t* order_key) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int v = memb[i], s = sub[v];
+    if (!inactive[s]) { order_key[v] = v - sub_ptr[s]; return; }                     // :342-343
+    const int c = cidx[i] + is_start[i] - 1;
+    if (2 * (int64_t)(cptr[c + 1] - cptr[c]) >= (int64_t)(sub_ptr[s + 1] - sub_ptr[s])) order_key[v] = i - cptr[c];
+}
+
+// one thread per set-ordered component: nx.weakly_connected_components' set(_plain_bfs(G, root))
+// from the component's first node -- per level node the successors in out_slot order, then the
+// predecessors in slot order, over edges with act != 0 -- then the copy's node order = the
+// order of a second set filled from the first (show_nodes(set(c))). The queue is the
+// component's own segment of an N-long array.
+__global__ void __launch_bounds__(BLOCK) k_ord_walk(gtf_graph g, const uint8_t* act, int n, const int32_t* n_comp,
+                                                    const int32_t* cptr, const int32_t* memb,
+                                                    const int32_t* so_flag, const int64_t* node_id,
+                                                    const uint64_t* ids, const int32_t* idx, const int64_t* toff,
+                                                    int64_t* tbl, int64_t tbl_words, int32_t* queue, uint8_t* seen,
+                                                    int32_t* order_key, int32_t* err) {
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= *n_comp || !so_flag[c]) return;
+    const int32_t lo = cptr[c], sz = cptr[c + 1] - lo;
+    const int64_t cap = set_capacity(sz);
+    if (toff[c] + 3 * cap > tbl_words) { atomicOr(err, OERR_OVER); return; }
+    int64_t* t = tbl + toff[c];
+    DevSet s;
+    s.init(t, t + cap, cap);
+    const int32_t root = memb[lo];
+    int32_t head = lo, tail = lo;
+    bool full = false;
+    auto visit = [&](int32_t w) {
+        if (seen[w]) return;
+        if (tail >= lo + sz) { full = true; return; }     // (cannot happen: the walk and the hooks use one edge rule)
+        seen[w] = 1;
+        s.add(node_id[w]);
+        queue[tail++] = w;
+    };
+    visit(root);
+    while (head < tail && !full) {
+        const int32_t v = queue[head++];
+        for (int32_t j = g.out_ptr[v]; j < g.out_ptr[v + 1]; j++) {
+            const int32_t k = g.out_slot[j];
+            if (act[k] != 0) visit(g.slot_dst[k]);                         // successors, G order
+        }
+        for (int32_t k = g.slot_ptr[v]; k < g.slot_ptr[v + 1]; k++)
+            if (g.is_edge[k] && act[k] != 0) visit(g.slot_src[k]);        // predecessors
+    }
+    DevSet shown;
+    int64_t* spare = (s.a == t) ? t + cap : t;   // the first set's spare table
+    shown.init(spare, t + 2 * cap, cap);
+    for (int64_t i = 0; i <= s.mask; i++)
+        if (s.a[i] >= 0) shown.add(s.a[i]);
+    if (full || s.over || shown.over) { atomicOr(err, OERR_OVER); return; }
+    int32_t r = 0;
+    for (int64_t i = 0; i <= shown.mask; i++) {
+        if (shown.a[i] < 0) continue;
+        const int32_t v = find_id(ids, idx, n, shown.a[i]);
+        if (v >= 0) order_key[v] = r;
+        r++;
+    }
+}
+
+struct OrdWs {
+    uint64_t *keys_in, *keys_out, *ids;
+    int32_t *vals_in, *memb, *idx, *is_start, *cidx, *cptr, *label, *queue, *so_flag, *so_size, *scal;
+    int64_t *words, *toff, *tbl;
+    uint8_t *seen, *inactive;
+    void* cub;
+    size_t cub_bytes, tbl_words, total;
+};
+
+size_t ord_cub_bytes(int n) {
+    size_t a = cub_bytes(n), b = 0, c = 0, d = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, n + 1);
+    (void)hipcub::DeviceReduce::Sum(nullptr, c, (int32_t*)nullptr, (int32_t*)nullptr, n);
+    (void)hipcub::DeviceReduce::Max(nullptr, d, (int32_t*)nullptr, (int32_t*)nullptr, n);
+    a = a > b ? a : b;
+    a = a > c ? a : c;
+    return a > d ? a : d;
+}
+
+// n >= 1. The set tables: a set of k distinct keys has a table of <= 8 max(k, 1) entries and a
+// component takes three, so <= 24 N words (the bound argued in gtf_build_dev.hip's carve)
+OrdWs carve_ord(void* base, int n, int n_sub) {
+    char* p = (char*)base;
+    OrdWs w;
+    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
+    const size_t n1 = (size_t)n + 1;
+    w.keys_in = (uint64_t*)take(8 * (size_t)n);
+    w.keys_out = (uint64_t*)take(8 * (size_t)n);
+    w.ids = (uint64_t*)take(8 * (size_t)n);
+    w.words = (int64_t*)take(8 * n1);
+    w.toff = (int64_t*)take(8 * n1);
+    w.vals_in = (int32_t*)take(4 * (size_t)n);
+    w.memb = (int32_t*)take(4 * (size_t)n);
+    w.idx = (int32_t*)take(4 * (size_t)n);
+    w.is_start = (int32_t*)take(4 * (size_t)n);
+    w.cidx = (int32_t*)take(4 * (size_t)n);
+    w.cptr = (int32_t*)take(4 * n1);
+    w.label = (int32_t*)take(4 * (size_t)n);
+    w.queue = (int32_t*)take(4 * (size_t)n);
+    w.so_flag = (int32_t*)take(4 * (size_t)n);
+    w.so_size = (int32_t*)take(4 * (size_t)n);
+    w.scal = (int32_t*)take(64);
+    w.seen = (uint8_t*)take((size_t)n);
+    w.inactive = (uint8_t*)take((size_t)(n_sub > 0 ? n_sub : 1));
+    w.cub_bytes = ord_cub_bytes(n);
+    w.cub = take(w.cub_bytes);
+    w.tbl_words = 24 * (size_t)n;
+    w.tbl = (int64_t*)take(8 * w.tbl_words);
+    w.total = (size_t)(p - (char*)base) + 256;
+    return w;
+}
+
+// ------------------------------------------------------------------ outputs
+__global__ void __launch_bounds__(BLOCK) k_out_notext(int n, const uint8_t* extracted, int32_t* notext) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v <= n) notext[v] = (v < n && !extracted[v]) ? 1 : 0;
+}
+
+// per subgraph: left, and (1 << 32 | left) where it is a remaining / a fragment subgraph, so
+// one 64-bit exclusive sum gives both the subgraph's place in its list and its first node's
+__global__ void __launch_bounds__(BLOCK) k_out_sub(int n_sub, int fragment, const int32_t* sub_ptr,
+                                                   const int32_t* pre, int32_t* left, int64_t* rem, int64_t* frag) {
+    const int s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s > n_sub) return;
+    const int l = s < n_sub ? pre[sub_ptr[s + 1]] - pre[sub_ptr[s]] : 0;
+    if (s < n_sub) left[s] = l;
+    rem[s] = l >= fragment ? ((int64_t)1 << 32) | l : 0;
+    frag[s] = (l > 0 && l < fragment) ? ((int64_t)1 << 32) | l : 0;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_out_cand(int n, const int32_t* n_cand, const int32_t* cand_ptr,
+                                                    const int32_t* members, const int32_t* label,
+                                                    const int8_t* status, int64_t* ext) {
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c > n) return;
+    int64_t e = 0;
+    if (c < *n_cand && status[label[members[cand_ptr[c]]]] == EX_EXTRACTED)
+        e = ((int64_t)1 << 32) | (cand_ptr[c + 1] - cand_ptr[c]);
+    ext[c] = e;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_out_nodes(int n, int n_sub, int fragment, gtf_extract_io io,
+                                                     gtf_extract_out o, const int32_t* pre, const int64_t* rem,
+                                                     const int64_t* frag) {
+    const int v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v >= n) return;
+    const int s = io.sub_id[v];
+    const int l = o.left[s];
+    const bool kept = !io.extracted[v] && l >= fragment;
+    o.keep[v] = kept ? 1 : 0;
+    if (io.extracted[v] || l == 0) return;
+    const int at = pre[v] - pre[io.sub_ptr[s]];          // among the subgraph's nodes that stay
+    const bool first = at == 0;
+    if (l >= fragment) {
+        const int pos = (int)(rem[s] & 0xffffffff) + at;
+        if (o.rem_nodes) o.rem_nodes[pos] = v;
+        if (o.rem_ids) o.rem_ids[pos] = o.node_id[v];
+        if (first && o.rem_ptr) o.rem_ptr[rem[s] >> 32] = pos;
+    } else {
+        const int pos = (int)(frag[s] & 0xffffffff) + at;
+        if (o.frag_nodes) o.frag_nodes[pos] = v;
+        if (o.frag_ids) o.frag_ids[pos] = o.node_id[v];
+        if (first && o.frag_ptr) o.frag_ptr[frag[s] >> 32] = pos;
+    }
+}
+
+// every position i of the extraction's sorted member list
+__global__ void __launch_bounds__(BLOCK) k_out_members(int n, gtf_extract_io io, gtf_extract_out o,
+                                                       const int32_t* members, const int32_t* is_start,
+                                                       const int32_t* cidx, const int32_t* cand_ptr,
+                                                       const int64_t* ext) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int c = cidx[i] + is_start[i] - 1;
+    if (ext[c + 1] == ext[c]) return;                    // not extracted
+    const int v = members[i];
+    const int pos = (int)(ext[c] & 0xffffffff) + (i - cand_ptr[c]);
+    if (o.cand_members) o.cand_members[pos] = v;
+    if (o.cand_ids) o.cand_ids[pos] = o.node_id[v];
+    if (is_start[i]) {
+        const int k = (int)(ext[c] >> 32), root = io.label[v];
+        if (o.cand_ptr) o.cand_ptr[k] = pos;
+        if (o.pval_xy) o.pval_xy[k] = io.pval_xy[root];
+        if (o.pval_zr) o.pval_zr[k] = io.pval_zr[root];
+    }
+}
+
+// the six counts, and the closing pointer of every list
+__global__ void k_out_counts(int n, int n_sub, gtf_extract_out o, const int64_t* ext, const int64_t* rem,
+                             const int64_t* frag, int32_t* counts) {
+    if (blockIdx.x || threadIdx.x) return;
+    const int64_t t[3] = {ext[n], rem[n_sub], frag[n_sub]};
+    int32_t* ptr[3] = {o.cand_ptr, o.rem_ptr, o.frag_ptr};
+    for (int k = 0; k < 3; k++) {
+        counts[2 * k] = (int32_t)(t[k] >> 32);
+        counts[2 * k + 1] = (int32_t)(t[k] & 0xffffffff);
+        if (ptr[k]) ptr[k][t[k] >> 32] = (int32_t)(t[k] & 0xffffffff);
+    }
+}
+
+struct OutWs {
+    int32_t *notext, *pre, *scal;
+    int64_t *in64, *ext, *rem, *frag, *frag_in;
+    void* cub;
+    size_t cub_bytes, total;
+};
+
+size_t out_cub_bytes(int m) {
+    size_t a = 0, b = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (int32_t*)nullptr, (int32_t*)nullptr, m + 1);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, m + 1);
+    return a > b ? a : b;
+}
+
+OutWs carve_out(void* base, int n, int n_sub) {
+    char* p = (char*)base;
+    OutWs w;
+    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
+    const size_t n1 = (size_t)n + 1, s1 = (size_t)n_sub + 1, m1 = n1 > s1 ? n1 : s1;
+    w.in64 = (int64_t*)take(8 * m1);
+    w.frag_in = (int64_t*)take(8 * s1);
+    w.ext = (int64_t*)take(8 * n1);
+    w.rem = (int64_t*)take(8 * s1);
+    w.frag = (int64_t*)take(8 * s1);
+    w.notext = (int32_t*)take(4 * n1);
+    w.pre = (int32_t*)take(4 * n1);
+    w.scal = (int32_t*)take(64);
+    w.cub_bytes = out_cub_bytes((int)(m1 - 1));
+    w.cub = take(w.cub_bytes);
+    w.total = (size_t)(p - (char*)base) + 256;
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gtf_subgraph_ptr_device(const int32_t* sub_id, int32_t n_nodes, int32_t n_sub, int32_t* sub_ptr,
+                            gtf_stream_t stream) {
+    if (!sub_ptr || n_nodes < 0 || n_sub < 0 || (n_nodes && !sub_id) || (n_nodes > 0 && n_sub == 0)) {
+        gtf::set_error("gtf_subgraph_ptr_device: bad arguments");
+        return -2;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_nodes == 0) {
+        if (hipMemsetAsync(sub_ptr, 0, 4 * ((size_t)n_sub + 1), st) != hipSuccess) { gtf::set_error("gtf_subgraph_ptr_device: memset"); return -1; }
+        return 0;
+    }
+    int32_t last = n_nodes;
+    bool ok = hipMemcpyAsync(sub_ptr + n_sub, &last, 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    hipLaunchKernelGGL(k_sub_ptr, dim3(grid(n_nodes)), dim3(BLOCK), 0, st, n_nodes, n_sub, sub_id, sub_ptr,
+                       sub_ptr + n_sub);
+    ok = ok && hipMemcpyAsync(&last, sub_ptr + n_sub, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) { gtf::set_error("gtf_subgraph_ptr_device: launch failed"); return -1; }
+    if (last != n_nodes) {
+        gtf::set_error("gtf_subgraph_ptr_device: sub_id must number the subgraphs 0 .. n_sub - 1 with the nodes grouped");
+        return -2;
+    }
+    return 0;
+}
+
+size_t gtf_candidate_order_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_sub) {
+    (void)n_slots;    // (the slot arrays are read in place)
+    return carve_ord(nullptr, n_nodes > 0 ? n_nodes : 1, n_sub > 0 ? n_sub : 0).total;
+}
+
+int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id,
+                               const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
+                               int32_t* order_key, void* workspace, size_t workspace_bytes,
+                               gtf_order_counts* counts, gtf_stream_t stream) {
+    const char* who = "gtf_candidate_order_device";
+    if (int rc = gtf::check_abi(g, who)) return rc;
+    if (!e || !counts || !workspace || g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0 || n_sub < 0) {
+        gtf::set_error("gtf_candidate_order_device: null argument or negative size");
+        return -2;
+    }
+    *counts = gtf_order_counts{0, 0, 0, 0};
+    const int n = g->n_nodes;
+    if (n == 0) return 0;
+    if (!sub_id || !sub_ptr || !node_id || !order_key || !g->slot_ptr || !g->out_ptr ||
+        (g->n_slots && (!g->slot_src || !g->slot_dst || !g->is_edge || !e->act)) || (g->n_edges && !g->out_slot)) {
+        gtf::set_error("gtf_candidate_order_device: missing array (slot_ptr, slot_src, slot_dst, out_ptr, out_slot, "
+                       "is_edge, act, sub_id, sub_ptr, node_id, order_key)");
+        return -2;
+    }
+    if (workspace_bytes < gtf_candidate_order_workspace_bytes(n, g->n_slots, n_sub)) {
+        gtf::set_error("gtf_candidate_order_device: workspace smaller than gtf_candidate_order_workspace_bytes");
+        return -2;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    OrdWs w = carve_ord(workspace, n, n_sub);
+    auto fail = [&](const char* what) { gtf::set_error(what); return -1; };
+#define GTF_CK(x, what) \
+    if ((x) != hipSuccess) return fail("gtf_candidate_order_device: " what)
+    GTF_CK(hipMemsetAsync(w.scal, 0, 64, st), "memset");
+    if (int rc = cca_rounds<true>(g, e, sub_id, n_sub, w.label, w.inactive, w.scal + 8, st,
+                                  "gtf_candidate_order_device: CCA round failed",
+                                  "gtf_candidate_order_device: CCA did not converge"))
+        return rc;
+    // members of every component in node order, the component pointers and their count
+    hipLaunchKernelGGL(k_ord_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.label, w.keys_in, w.vals_in, w.seen);
+    size_t cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys_out, w.vals_in, w.memb, n, 0, 64, st),
+           "sort members");
+    hipLaunchKernelGGL(k_ex_starts, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.keys_out, w.is_start);
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.is_start, w.cidx, n, st), "scan");
+    hipLaunchKernelGGL(k_ex_ptr, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.is_start, w.cidx, w.cptr, w.scal + OS_NCOMP);
+    hipLaunchKernelGGL(k_ord_rank, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.memb, w.is_start, w.cidx, w.cptr, sub_id,
+                       sub_ptr, w.inactive, order_key);
+    // node id -> index (keys_in is free again; vals_in still holds 0 .. n - 1)
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, (const uint64_t*)node_id, w.ids, w.vals_in, w.idx, n, 0, 64,
+                                              st), "sort ids");
+    hipLaunchKernelGGL(k_ord_check_ids, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.ids, w.scal + OS_ERR);
+    // the set-ordered components: table offsets and counts by scans, then one thread each
+    hipLaunchKernelGGL(k_ord_words, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, w.scal + OS_NCOMP, w.cptr, w.memb,
+                       sub_id, sub_ptr, w.inactive, w.words, w.so_flag, w.so_size);
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.words, w.toff, n + 1, st), "scan");
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceReduce::Sum(w.cub, cb, w.so_flag, w.scal + OS_NSET, n, st), "sum");
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceReduce::Max(w.cub, cb, w.so_size, w.scal + OS_MAXSET, n, st), "max");
+    hipLaunchKernelGGL(k_ord_walk, dim3(grid(n)), dim3(BLOCK), 0, st, *g, e->act, n, w.scal + OS_NCOMP, w.cptr, w.memb,
+                       w.so_flag, node_id, w.ids, w.idx, w.toff, w.tbl, (int64_t)w.tbl_words, w.queue, w.seen,
+                       order_key, w.scal + OS_ERR);
+    GTF_CK(hipGetLastError(), "launch");
+    int32_t scal[4];
+    GTF_CK(hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st), "read");
+    GTF_CK(hipStreamSynchronize(st), "sync");
+#undef GTF_CK
+    if (scal[OS_ERR] & OERR_RANGE) { gtf::set_error("gtf_candidate_order_device: node ids must be in [0, 2^61 - 1)"); return -2; }
+    if (scal[OS_ERR] & OERR_DUP) { gtf::set_error("gtf_candidate_order_device: duplicate node id"); return -2; }
+    if (scal[OS_ERR] & OERR_OVER) {
+        gtf::set_error("gtf_candidate_order_device: a set held more keys than its table was sized for");
+        return -1;
+    }
+    *counts = gtf_order_counts{scal[OS_NCOMP], scal[OS_NSET], scal[OS_MAXSET], 0};
+    return 0;
+}
+
+size_t gtf_extract_outputs_workspace_bytes(int32_t n_nodes, int32_t n_sub) {
+    return carve_out(nullptr, n_nodes > 0 ? n_nodes : 1, n_sub > 0 ? n_sub : 0).total;
+}
+
+int gtf_extract_outputs(const gtf_graph* g, const gtf_extract_io* io, int32_t fragment,
+                        const void* extract_workspace, const gtf_extract_out* out, void* workspace,
+                        size_t workspace_bytes, gtf_extract_out_counts* counts, gtf_stream_t stream) {
+    if (int rc = gtf::check_abi(g, "gtf_extract_outputs")) return rc;
+    if (!io || !out || !counts || !workspace || !extract_workspace || g->n_nodes < 0 || fragment < 1) {
+        gtf::set_error("gtf_extract_outputs: null argument, negative size or fragment < 1");
+        return -2;
+    }
+    *counts = gtf_extract_out_counts{0, 0, 0, 0, 0, 0};
+    const int n = g->n_nodes, n_sub = io->n_sub;
+    if (n == 0) return 0;
+    if (!io->sub_id || !io->sub_ptr || !io->label || !io->status || !io->pval_xy || !io->pval_zr || !io->extracted ||
+        !io->n_candidates || n_sub <= 0 || !out->left || !out->keep ||
+        ((out->cand_ids || out->rem_ids || out->frag_ids) && !out->node_id)) {
+        gtf::set_error("gtf_extract_outputs: missing arrays (the results of gtf_extract_candidates, left, keep, "
+                       "node_id for the id lists)");
+        return -2;
+    }
+    if (workspace_bytes < gtf_extract_outputs_workspace_bytes(n, n_sub)) {
+        gtf::set_error("gtf_extract_outputs: workspace smaller than gtf_extract_outputs_workspace_bytes");
+        return -2;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const ExWs x = carve_ex(const_cast<void*>(extract_workspace), n, n_sub);
+    OutWs w = carve_out(workspace, n, n_sub);
+    auto fail = [&](const char* what) { gtf::set_error(what); return -1; };
+#define GTF_CK(x, what) \
+    if ((x) != hipSuccess) return fail("gtf_extract_outputs: " what)
+    // nodes that stay, counted before every node: left[s] is a difference at sub_ptr
+    hipLaunchKernelGGL(k_out_notext, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, io->extracted, w.notext);
+    size_t cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.notext, w.pre, n + 1, st), "scan");
+    hipLaunchKernelGGL(k_out_sub, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, n_sub, fragment, io->sub_ptr, w.pre,
+                       out->left, w.in64, w.frag_in);
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in64, w.rem, n_sub + 1, st), "scan");
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.frag_in, w.frag, n_sub + 1, st), "scan");
+    hipLaunchKernelGGL(k_out_nodes, dim3(grid(n)), dim3(BLOCK), 0, st, n, n_sub, fragment, *io, *out, w.pre, w.rem,
+                       w.frag);
+    // the extracted candidates, in the order the extraction's sort left them
+    hipLaunchKernelGGL(k_out_cand, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, io->n_candidates, x.cand_ptr, x.vals_out,
+                       io->label, io->status, w.in64);
+    cb = w.cub_bytes;
+    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in64, w.ext, n + 1, st), "scan");
+    hipLaunchKernelGGL(k_out_members, dim3(grid(n)), dim3(BLOCK), 0, st, n, *io, *out, x.vals_out, x.is_start, x.cidx,
+                       x.cand_ptr, w.ext);
+    hipLaunchKernelGGL(k_out_counts, dim3(1), dim3(64), 0, st, n, n_sub, *out, w.ext, w.rem, w.frag, w.scal);
+    GTF_CK(hipGetLastError(), "launch");
+    int32_t c[6];
+    GTF_CK(hipMemcpyAsync(c, w.scal, sizeof(c), hipMemcpyDeviceToHost, st), "read");
+    GTF_CK(hipStreamSynchronize(st), "sync");
+#undef GTF_CK
+    *counts = gtf_extract_out_counts{c[0], c[1], c[2], c[3], c[4], c[5]};
+    return 0;
+}
 
 size_t gtf_extract_workspace_bytes(int32_t n_nodes, int32_t n_sub) {
     const int n = n_nodes > 0 ? n_nodes : 1;
@@ -534,27 +1045,10 @@ int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_ext
     }
     hipStream_t st = (hipStream_t)stream;
     ExWs w = carve_ex(workspace, n, io->n_sub);
-    const int nb = grid(n > io->n_sub ? n : io->n_sub);
-    hipLaunchKernelGGL(k_ex_init, dim3(nb), dim3(BLOCK), 0, st, n, io->n_sub, io->label, w.inactive, w.flag);
-    if (g->n_slots > 0)
-        hipLaunchKernelGGL(k_ex_inactive, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, io->sub_id,
-                           w.inactive);
-    // hook + compress until no root changes (candidates are short: a few rounds)
-    int32_t changed = 0;
-    for (int round = 0; round < 64; round++) {
-        int32_t zero = 0;
-        if (hipMemcpyAsync(w.flag, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-        if (g->n_slots > 0)
-            hipLaunchKernelGGL(k_ex_hook, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, io->label, w.flag);
-        hipLaunchKernelGGL(k_ex_compress, dim3(grid(n)), dim3(BLOCK), 0, st, n, io->label);
-        if (hipMemcpyAsync(&changed, w.flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            gtf::set_error("gtf_extract_candidates: CCA round failed");
-            return -1;
-        }
-        if (!changed) break;
-    }
-    if (changed) { gtf::set_error("gtf_extract_candidates: CCA did not converge"); return -1; }
+    if (int rc = cca_rounds<false>(g, e, io->sub_id, io->n_sub, io->label, w.inactive, w.flag, st,
+                                   "gtf_extract_candidates: CCA round failed",
+                                   "gtf_extract_candidates: CCA did not converge"))
+        return rc;
     hipLaunchKernelGGL(k_ex_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, io->sub_id, io->sub_ptr, w.inactive,
                        io->order_key, io->label, w.keys_in, w.vals_in);
     size_t cb = w.cub_bytes;

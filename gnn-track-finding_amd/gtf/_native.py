@@ -114,6 +114,23 @@ class GtfExtractIO(ctypes.Structure):
                 ("extracted", P), ("n_candidates", P)]
 
 
+class GtfOrderCounts(ctypes.Structure):
+    """gtf_order_counts: what gtf_candidate_order_device met"""
+    _fields_ = [("n_components", I32), ("n_set_ordered", I32), ("max_set_ordered", I32), ("pad_", I32)]
+
+
+class GtfExtractOut(ctypes.Structure):
+    """gtf_extract_out: the caller-allocated outputs of gtf_extract_outputs (NULL = not wanted)"""
+    _fields_ = [("left", P), ("keep", P), ("cand_ptr", P), ("cand_members", P), ("pval_xy", P), ("pval_zr", P),
+                ("rem_ptr", P), ("rem_nodes", P), ("frag_ptr", P), ("frag_nodes", P), ("node_id", P),
+                ("cand_ids", P), ("rem_ids", P), ("frag_ids", P)]
+
+
+class GtfExtractOutCounts(ctypes.Structure):
+    _fields_ = [("n_extracted", I32), ("n_extracted_nodes", I32), ("n_remaining", I32), ("n_remaining_nodes", I32),
+                ("n_fragments", I32), ("n_fragment_nodes", I32)]
+
+
 class GtfEventCsr(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int64), ("n_rows", ctypes.c_int64), ("node_id", P), ("row_a", P),
                 ("row_b", P), ("order", P), ("sub_id", P), ("slot_ptr", P), ("slot_src", P), ("tse_rank", P),
@@ -180,6 +197,8 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_shard_chunk_bytes", "gtf_shard_pack", "gtf_shard_unpack", "gtf_halo_pack", "gtf_halo_unpack",
            "gtf_extract_workspace_bytes",
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
+           "gtf_subgraph_ptr_device", "gtf_candidate_order_workspace_bytes", "gtf_candidate_order_device",
+           "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
@@ -250,6 +269,15 @@ def lib(lean: bool = False):
     L.gtf_extract_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_extract_workspace_bytes.argtypes = [I32, I32]
     L.gtf_extract_candidates.argtypes = [G, E, ctypes.POINTER(GtfExtractIO), ctypes.POINTER(GtfExtractParams), P, P]
+    L.gtf_subgraph_ptr_device.argtypes = [P, I32, I32, P, P]
+    L.gtf_candidate_order_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_candidate_order_workspace_bytes.argtypes = [I32, I32, I32]
+    L.gtf_candidate_order_device.argtypes = [G, E, P, P, I32, P, P, P, ctypes.c_size_t,
+                                             ctypes.POINTER(GtfOrderCounts), P]
+    L.gtf_extract_outputs_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_extract_outputs_workspace_bytes.argtypes = [I32, I32]
+    L.gtf_extract_outputs.argtypes = [G, ctypes.POINTER(GtfExtractIO), I32, P, ctypes.POINTER(GtfExtractOut), P,
+                                      ctypes.c_size_t, ctypes.POINTER(GtfExtractOutCounts), P]
     SH = ctypes.POINTER(GtfShard)
     L.gtf_pass_shard.argtypes = [G, N, S, S, E, PR, SH, P, P, ctypes.POINTER(P)]
     L.gtf_tag_sweep_shard.argtypes = [G, P, P, P, P, SH, I32, I32, P]
@@ -313,7 +341,8 @@ def lib(lean: bool = False):
                "gtf_comm_unique_id", "gtf_comm_init", "gtf_comm_destroy", "gtf_comm_rank", "gtf_comm_size",
                "gtf_halo_exchange", "gtf_halo_alltoall", "gtf_allreduce_max_i64", "gtf_allgather_bytes",
                "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
-               "gtf_subset_gather", "gtf_refresh_send_mw"):
+               "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
+               "gtf_extract_outputs"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -270,6 +270,7 @@ class DeviceGraph:
         elif layout != "natural":
             raise ValueError("layout must be 'natural', 'schedule', 'tiled' or 'padded'")
         self.slot_ptr_host = g.slot_ptr
+        self._node_id_host = g.node["node_id"]   # uploaded on first need (node_id_dev)
         self.torch = torch
         if torch is not None:
             self.device = torch.device(device)
@@ -868,7 +869,19 @@ class DeviceGraph:
             raise ValueError("%s must have %d elements" % (what, n))
         return t
 
-    def subset(self, keep, gnn=None) -> "DeviceGraph":
+    def node_id_dev(self):
+        """the node ids (int64 [N]) as a resident node column: uploaded on first need; a subset()
+        child of a graph that holds the column gets it through the gather"""
+        if "node_id" not in self.t:
+            if getattr(self, "_node_id_host", None) is None:
+                raise ValueError("this DeviceGraph holds no node ids (a subset() child of a parent without the "
+                                 "resident column: call node_id_dev() on the parent first)")
+            if self.layout != "natural":
+                raise NotImplementedError("node_id_dev: only layout='natural'")
+            self.t["node_id"] = self._dev_from(np.ascontiguousarray(self._node_id_host, np.int64))
+        return self.t["node_id"]
+
+    def subset(self, keep, gnn=None, carry=None) -> "DeviceGraph":
         """The graph after removing the nodes whose `keep` is false, built on the device:
         gtf.graph.subset (extract_track_candidates.py:459-467), array for array, by
         gtf_graph_subset_plan / _apply and gtf_subset_gather, with the child's schedules and
@@ -876,7 +889,10 @@ class DeviceGraph:
         keep: host bool [N] or device uint8 [N] in this graph's node order; gnn: optional
         [N, 4] replacement of the GNN coordinates (host or device) -- the extraction's
         close-proximity merge. The child's uts_fresh is 0 in both bits: its entries read
-        their stored xyzr until the next message passing rewrites them. Natural layout only."""
+        their stored xyzr until the next message passing rewrites them. Natural layout only.
+        carry: {name: [N, ...] array} of the caller's own node-axis columns (host, or device of
+        this graph's allocator), gathered with the payload; the child holds them as device arrays
+        in ``carried``. The resident node_id column (node_id_dev) travels the same way."""
         if self.layout != "natural" or self.n_pack_waves:
             raise NotImplementedError("DeviceGraph.subset: only layout='natural' without pack=True (the renumbered, "
                                       "padded and packed layouts are not carried over); this graph has layout=%r, "
@@ -908,6 +924,24 @@ class DeviceGraph:
         c.n_nodes, c.n_slots, c.n_edges, c.n_sub, c._sub_ok = N2, S2, E2, cnt.n_sub, True
         c.tables = "device"
         c.t = {}
+        c._node_id_host, c.carried = None, {}
+        extra = []   # (source, destination, row bytes) of the node-axis columns beyond the graph's own
+        if "node_id" in self.t:
+            c.t["node_id"] = c._dev_empty(N2, np.int64)
+            extra.append((self.t["node_id"], c.t["node_id"], 8))
+        for name, a in (carry or {}).items():
+            if not hasattr(a, "data_ptr"):
+                a = np.ascontiguousarray(a)
+                dt = a.dtype
+                a = self._dev_from(a)
+            else:
+                dt = a.dtype if isinstance(a.dtype, np.dtype) else np.dtype(str(a.dtype).split(".")[-1])
+                a = a if self.torch is None else a.contiguous().reshape(-1)
+            if N and a.numel() % N:
+                raise ValueError("carry[%r] must have one row per node" % name)
+            width = a.numel() // N if N else 1
+            c.carried[name] = c._dev_empty(N2 * width, dt)
+            extra.append((a, c.carried[name], width * np.dtype(dt).itemsize))
         struct = [("node_map", N2, np.int32), ("slot_map", S2, np.int32), ("slot_ptr", N2 + 1, np.int32),
                   ("slot_src", S2, np.int32), ("out_ptr", N2 + 1, np.int32), ("out_slot", E2, np.int32),
                   ("sub_id", N2, np.int32), ("solo", N2, np.uint8)]
@@ -928,6 +962,8 @@ class DeviceGraph:
                 if rows:
                     cols.append(nat.GtfColumn(vp(src), c.ptr(f), width * np.dtype(dt).itemsize,
                                               self.SUBSET_FILL.get(f, nat.COL_COPY) if axis else nat.COL_COPY))
+            if axis == 0 and rows:
+                cols += [nat.GtfColumn(vp(a), vp(b), rb, nat.COL_COPY) for a, b, rb in extra if rb]
             if cols:
                 arr = (nat.GtfColumn * len(cols))(*cols)
                 nat.check(L.gtf_subset_gather(vp(ws), axis, arr, len(cols), self.stream))

@@ -96,6 +96,118 @@ def _zeros(d, nbytes):
     return d.torch.zeros(nbytes, dtype=d.torch.uint8, device=d.device)
 
 
+# ---------------------------------------------------------------- on a DeviceGraph's own buffers
+def _vp(x):
+    return ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+
+def sub_ptr_dev(d):
+    """the first node of every subgraph ([n_sub + 1] int32 on the device) from d's sub_id, by
+    gtf_subgraph_ptr_device; built once per DeviceGraph"""
+    if "sub_ptr" not in d.t:
+        if d.layout != "natural":
+            raise NotImplementedError("the device extraction needs layout='natural'")
+        t = d._dev_empty(d.n_sub + 1, np.int32)
+        nat.check(d.lib.gtf_subgraph_ptr_device(d.ptr("sub_id"), d.n_nodes, d.n_sub, _vp(t), d.stream))
+        d.t["sub_ptr"] = t
+    return d.t["sub_ptr"]
+
+
+def candidate_order_dev(d, counts=None):
+    """candidate_order() on the device (gtf_candidate_order_device), from the DeviceGraph's own
+    arrays: the activation mask a stage just left, sub_id, and the resident node_id column
+    (uploaded on first need). Returns the order keys as a device int32 [N] array; counts: an
+    optional dict that receives gtf_order_counts (components, set-ordered ones, the largest)."""
+    N = d.n_nodes
+    sp, nid = sub_ptr_dev(d), d.node_id_dev()
+    order = d._dev_empty(max(N, 1), np.int32)
+    nb = int(d.lib.gtf_candidate_order_workspace_bytes(N, d.n_slots, d.n_sub))
+    ws = d._dev_empty(nb, np.uint8)
+    cnt = nat.GtfOrderCounts()
+    nat.check(d.lib.gtf_candidate_order_device(ctypes.byref(d.cg_sched), ctypes.byref(d.ce), d.ptr("sub_id"), _vp(sp),
+                                               d.n_sub, _vp(nid), _vp(order), _vp(ws), ctypes.c_size_t(nb),
+                                               ctypes.byref(cnt), d.stream))
+    if counts is not None:
+        counts.update(n_components=cnt.n_components, n_set_ordered=cnt.n_set_ordered,
+                      max_set_ordered=cnt.max_set_ordered)
+    return order
+
+
+def run_dev(d, vivl_dev, params: Params, order_dev=None):
+    """run() on the DeviceGraph's own buffers: xyzr, sub_id and the activation mask are read
+    where they lie, the merge mutation goes into a device copy of gnn, nothing is uploaded from
+    a host graph. vivl_dev: device float64 [N * 2]; order_dev: device int32 [N] (candidate_order_dev)
+    or None. Returns device arrays: label, status, pxy, pzr, ext, gnn, ncand, and the workspace
+    ("ws") that outputs_dev reads the sorted member list from."""
+    if params.numhits < 3:
+        raise ValueError("numhits must be >= 3 (rotate_track reads three hits)")
+    N, n1 = d.n_nodes, max(d.n_nodes, 1)
+    if vivl_dev.numel() != 2 * N:
+        raise ValueError("vivl must have one (volume, layer) row per node")
+    sp = sub_ptr_dev(d)
+    gnn = d._dev_empty(4 * N, np.float64)
+    if N:
+        nat.check(d.lib.gtf_memcpy_dtod(_vp(gnn), d.ptr("gnn"), ctypes.c_size_t(32 * N), d.stream))
+    t = {"gnn": gnn, "label": d._dev_zeros(n1, np.int32), "status": d._dev_empty(n1, np.int8),
+         "pxy": d._dev_empty(n1, np.float64), "pzr": d._dev_empty(n1, np.float64),
+         "ext": d._dev_zeros(n1, np.uint8), "ncand": d._dev_zeros(1, np.int32)}
+    nat.check(d.lib.gtf_memset(_vp(t["status"]), 0xFF, ctypes.c_size_t(n1), d.stream))          # -1
+    for k in ("pxy", "pzr"):
+        nat.check(d.lib.gtf_memset(_vp(t[k]), 0xFF, ctypes.c_size_t(8 * n1), d.stream))         # NaN
+    t["ws"] = d._dev_empty(int(d.lib.gtf_extract_workspace_bytes(N, d.n_sub)), np.uint8)
+    io = nat.GtfExtractIO(d.ptr("xyzr"), _vp(vivl_dev), d.ptr("sub_id"), _vp(sp), d.n_sub, 0, _vp(order_dev),
+                          _vp(gnn), _vp(t["label"]), _vp(t["status"]), _vp(t["pxy"]), _vp(t["pzr"]), _vp(t["ext"]),
+                          _vp(t["ncand"]))
+    cp = params.c()
+    nat.check(d.lib.gtf_extract_candidates(ctypes.byref(d.cg), ctypes.byref(d.ce), ctypes.byref(io),
+                                           ctypes.byref(cp), _vp(t["ws"]), d.stream))
+    t["io"] = io
+    return t
+
+
+def _groups(ptr, members):
+    return [members[ptr[i]:ptr[i + 1]] for i in range(len(ptr) - 1)]
+
+
+def outputs_dev(d, res, fragment, ids=True):
+    """outputs() on the device (gtf_extract_outputs) from run_dev's result, which must not have
+    been reused since. Returns the dict outputs() returns -- the lists as host arrays: of node
+    ids (int64) with ids=True, of node indices with ids=False -- plus "keep", the device uint8
+    [N] mask DeviceGraph.subset takes, and "left" [n_sub] on the device. Only the counts, the
+    pointers, the p-values and the lists asked for cross to the host."""
+    N, n1, S = d.n_nodes, max(d.n_nodes, 1), d.n_sub
+    o = {"left": d._dev_empty(max(S, 1), np.int32), "keep": d._dev_empty(n1, np.uint8),
+         "pval_xy": d._dev_empty(n1, np.float64), "pval_zr": d._dev_empty(n1, np.float64)}
+    for k in ("cand", "rem", "frag"):
+        o[k + "_ptr"] = d._dev_empty(n1 + 1, np.int32)
+        o[k + "_list"] = d._dev_empty(n1, np.int64 if ids else np.int32)
+    z = ctypes.c_void_p(0)
+    lists = [_vp(o[k + "_list"]) for k in ("cand", "rem", "frag")]
+    out = nat.GtfExtractOut(_vp(o["left"]), _vp(o["keep"]), _vp(o["cand_ptr"]), z if ids else lists[0],
+                            _vp(o["pval_xy"]), _vp(o["pval_zr"]), _vp(o["rem_ptr"]), z if ids else lists[1],
+                            _vp(o["frag_ptr"]), z if ids else lists[2], _vp(d.node_id_dev()) if ids else z,
+                            *(lists if ids else (z, z, z)))
+    nb = int(d.lib.gtf_extract_outputs_workspace_bytes(N, S))
+    ws = d._dev_empty(nb, np.uint8)
+    cnt = nat.GtfExtractOutCounts()
+    nat.check(d.lib.gtf_extract_outputs(ctypes.byref(d.cg), ctypes.byref(res["io"]), int(fragment), _vp(res["ws"]),
+                                        ctypes.byref(out), _vp(ws), ctypes.c_size_t(nb), ctypes.byref(cnt),
+                                        d.stream))
+
+    def host(t, n):   # the first n elements on the host
+        if n == 0:
+            return np.empty(0, t.dtype if d.torch is None else t.cpu().numpy().dtype)
+        return d._np(t[:n] if d.torch is not None else t.view(0, n, t.dtype))
+
+    r = {"keep": o["keep"], "left": o["left"]}
+    for k, key, n, m in (("cand", "extracted", cnt.n_extracted, cnt.n_extracted_nodes),
+                         ("rem", "remaining", cnt.n_remaining, cnt.n_remaining_nodes),
+                         ("frag", "fragments", cnt.n_fragments, cnt.n_fragment_nodes)):
+        r[key] = _groups(host(o[k + "_ptr"], n + 1), host(o[k + "_list"], m)) if N else []
+    r["pval_xy"], r["pval_zr"] = host(o["pval_xy"], cnt.n_extracted), host(o["pval_zr"], cnt.n_extracted)
+    return r
+
+
 def candidate_order(g: TrackGraph) -> np.ndarray:
     """Each node's position inside its candidate in the reference's member order
     (gtf_candidate_order: networkx CCA + subgraph-copy orders, :332-346), for run()'s

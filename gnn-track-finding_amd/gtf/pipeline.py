@@ -115,7 +115,7 @@ def _ids(g: TrackGraph, groups):
 
 def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
         device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host",
-        resident: bool = False) -> List[Iteration]:
+        resident=False) -> List[Iteration]:
     """Iterations ``first`` .. ``first + iterations - 1`` of the loop, starting from
     the stage input ``g`` (the event network for iteration 1). Stops early when
     nothing remains. keep_graphs: also return each iteration's stage output and
@@ -129,18 +129,28 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
     (extract.candidate_order, extract.outputs) stay on the host, so the download after every
     stage stays, and the next iteration's host graph is the child's to_host(): what this mode
     removes is the host subset, the host refresh, the re-upload and the second DeviceGraph of
-    even iterations. Same results, array for array."""
+    even iterations. Same results, array for array.
+    resident="device": the candidate order and the stage outputs run on the device as well
+    (extract.candidate_order_dev / run_dev / outputs_dev: gtf_candidate_order_device,
+    gtf_extract_candidates on the DeviceGraph's own buffers, gtf_extract_outputs), the keep mask
+    goes to DeviceGraph.subset without leaving HBM, and vivl and node_id travel as carried node
+    columns. No download, no host order or outputs, no to_host: per iteration the host receives
+    the counts, the candidate / remaining / fragment node-id lists and the p-values (and, with
+    keep_graphs, the graphs it asked for, downloaded after the step). Same Iteration records."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
+    if resident not in (False, True, "device"):
+        raise ValueError("resident must be False, True or 'device'")
     vivl = np.asarray(vivl, np.float64).reshape(-1, 2)
     if vivl.shape[0] != g.n_nodes:
         raise ValueError("vivl must have one row per node")
     out = []
     torch = None
     dnext = None   # resident: the DeviceGraph that already holds the iteration's input
+    vivl_dev = None   # resident="device": vivl beside it
     for it in range(first, first + iterations):
-        if g.n_nodes == 0:
+        if (dnext.n_nodes if resident == "device" and dnext is not None else g.n_nodes) == 0:
             break
         t0 = time.perf_counter()
         d = dnext if dnext is not None else DeviceGraph(g, device, tables=tables)
@@ -159,6 +169,34 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
         d.raise_errors()
         torch.cuda.synchronize(d.device)
         t1 = time.perf_counter()
+        if resident == "device":
+            if vivl_dev is None:
+                vivl_dev = d._dev_from(vivl)
+            order = extract.candidate_order_dev(d)
+            res = extract.run_dev(d, vivl_dev, ex, order)
+            t2 = time.perf_counter()
+            o = extract.outputs_dev(d, res, ex.numhits, ids=True)
+            dnext = d.subset(o["keep"], gnn=res["gnn"], carry={"vivl": vivl_dev})
+            dnext.refresh_send_mw()
+            if it % 2 == 0 and dnext.n_nodes:      # remove_state_metadata.py, as below
+                dnext.clear_errors()
+                dnext.update(p)
+                dnext.raise_errors()
+            t3 = time.perf_counter()
+            rec = Iteration(it, stage, o["extracted"], o["pval_xy"], o["pval_zr"], o["remaining"], o["fragments"],
+                            {"stage": t1 - t0, "extract": t2 - t1, "next": t3 - t2})
+            vivl_dev = dnext.carried["vivl"]
+            if keep_graphs:
+                # after the step (it left d's arrays as the stage wrote them). As the other modes:
+                # the iteration's input graph (the previous record's remaining_graph) ends holding
+                # the stage's output and the merged coordinates
+                net = d.download(g).copy()
+                g.node["gnn"] = d._np(res["gnn"]).reshape(-1, 4)
+                g = dnext.to_host(g)
+                rec.network, rec.remaining_graph = net, g
+                rec.remaining_vivl = d._np(vivl_dev).reshape(-1, 2)
+            out.append(rec)
+            continue
         d.download(g)
         order = extract.candidate_order(g)            # members in the reference's candidate order
         res = extract.run(g, vivl, ex, order_key=order, d=d)

@@ -60,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--resident", action="store_true",
                     help="cut each iteration's remaining graph on the GPU (DeviceGraph.subset) instead of on the host")
+    ap.add_argument("--resident-outputs", action="store_true",
+                    help="as --resident, and the candidate order and the stage outputs are computed on the GPU too "
+                         "(pipeline.run(resident='device')): only the id lists and p-values come back")
     ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
@@ -86,7 +89,7 @@ def main(argv=None):
         if vivl is None:
             raise SystemExit("remaining graph has no vivl array")
     its = pipeline.run(g, vivl, args.end - args.start + 1, p, ex, args.device, first=args.start, keep_graphs=True,
-                       resident=args.resident)
+                       resident="device" if args.resident_outputs else args.resident)
     for it in its:
         d = os.path.join(root, "iteration_%d" % it.index)
         store.save_graph(os.path.join(_dir(d, "network"), "graph.npz"), it.network)

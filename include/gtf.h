@@ -576,6 +576,92 @@ size_t gtf_extract_workspace_bytes(int32_t n_nodes, int32_t n_sub);
  * "CCA did not converge" when none of 64 rounds passed without a change */
 int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_extract_io* io,
                            const gtf_extract_params* p, void* workspace, gtf_stream_t stream);
+/* Workspace contract: after a successful call the workspace holds the member list sorted by
+ * (candidate id, order key) and the candidate pointers into it. gtf_extract_outputs (below)
+ * reads them there, for the same n_nodes and n_sub; they are valid until the caller reuses
+ * or frees the workspace. */
+
+/* ---- The extraction's inputs and outputs without the host (resident loop) ---------------
+ * gtf_subgraph_ptr_device: sub_ptr [n_sub + 1] (first node of each subgraph) from a device
+ * sub_id [N] that numbers the subgraphs 0, 1, 2, ... with the nodes grouped (pack() order, a
+ * gtf_graph_subset_apply result). Synchronises once; -2 when sub_id is not of that form or
+ * does not end at n_sub - 1. n_nodes == 0: every pointer is 0 (no synchronisation). */
+int gtf_subgraph_ptr_device(const int32_t* sub_id, int32_t n_nodes, int32_t n_sub, int32_t* sub_ptr,
+                            gtf_stream_t stream);
+
+/* gtf_candidate_order_device: gtf_candidate_order (below; extract_track_candidates.py:332-346)
+ * from device arrays, the same order_key [N] array for array. Reads n_nodes, n_slots,
+ * n_edges, slot_ptr, slot_src, slot_dst, out_ptr, out_slot and is_edge of *g, e->act, sub_id
+ * [N] / sub_ptr [n_sub + 1] (as gtf_extract_io) and node_id [N] (int64, device).
+ *   - a subgraph without an inactive edge: order_key[v] = v - sub_ptr[s] (:342-343);
+ *   - else the components over the edges with act != 0 (the host function's rule; the
+ *     extraction itself hooks act == 1), by the extraction's hook + compress rounds, their
+ *     members by one radix sort of (component, node index);
+ *   - a component of at least half its subgraph: the rank of the node index among its
+ *     members (G.subgraph(c) iterates G when 2|c| >= |G|);
+ *   - a smaller one ("set-ordered"): ONE THREAD walks the reference's BFS from the
+ *     component's first node (successors in out_slot order, then predecessors in slot
+ *     order), inserts node_id into a CPython 3.10 set, copies it into a second one
+ *     (show_nodes(set(c))) and ranks the nodes in that set's iteration order. A very large
+ *     component below half its subgraph is therefore slow but correct -- the limit of
+ *     gtf_build_event_csr_device's component order; counts->max_set_ordered reports the
+ *     largest one met.
+ * node ids must be distinct and in [0, 2^61 - 1) (gtf_build_event_csr_device's rule), checked
+ * on the device: -2. Null arguments (-2) and another ABI (-3) are decided on the host before
+ * any launch. Synchronises `stream` once per hook round and once at the end, when *counts
+ * is filled. n_nodes == 0: returns 0 with zero counts, nothing launched. */
+typedef struct gtf_order_counts {
+    int32_t n_components;      /* components over the act != 0 edges (whole graph) */
+    int32_t n_set_ordered;     /* of them: ordered by the one-thread set walk */
+    int32_t max_set_ordered;   /* nodes of the largest of those (0 when none) */
+    int32_t pad_;
+} gtf_order_counts;
+
+/* positive for an empty graph, non-decreasing in every argument (negative counts as 0); the
+ * set tables take <= 24 n_nodes words (3 tables of <= 8 max(k, 1) entries per component) */
+size_t gtf_candidate_order_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_sub);
+int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id,
+                               const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
+                               int32_t* order_key, void* workspace, size_t workspace_bytes,
+                               gtf_order_counts* counts, gtf_stream_t stream);
+
+/* gtf_extract_outputs: the stage's outputs (extract_track_candidates.py:423-430 the remaining
+ * and fragment subgraphs, :459-467 the node removal; gtf/extract.py outputs) from the results
+ * of a gtf_extract_candidates call: label, status, extracted, pval_xy, pval_zr, sub_id,
+ * sub_ptr, n_sub and n_candidates of *io, and the sorted member list and candidate pointers
+ * that call left in `extract_workspace` (see the contract above). Device pointers,
+ * caller-allocated at the upper bounds; all but left / keep may be NULL = not wanted. */
+typedef struct gtf_extract_out {
+    int32_t* left;           /* [n_sub]  nodes of each subgraph that were not extracted */
+    uint8_t* keep;           /* [N]      1 = not extracted and left[sub] >= fragment: gtf_graph_subset_plan's mask */
+    int32_t* cand_ptr;       /* [<= N+1] extracted candidates, in candidate-id order ... */
+    int32_t* cand_members;   /* [<= N]   ... members in order-key order */
+    double* pval_xy;         /* [<= N]   per extracted candidate, copied bit for bit */
+    double* pval_zr;
+    int32_t* rem_ptr;        /* [<= N+1] subgraphs with left >= fragment, in subgraph order ... */
+    int32_t* rem_nodes;      /* [<= N]   ... their nodes that were not extracted, in node order */
+    int32_t* frag_ptr;       /* [<= N+1] subgraphs with 0 < left < fragment */
+    int32_t* frag_nodes;     /* [<= N] */
+    const int64_t* node_id;  /* [N] or NULL; when set, the member arrays also as node ids: */
+    int64_t* cand_ids;       /* [<= N] */
+    int64_t* rem_ids;        /* [<= N] */
+    int64_t* frag_ids;       /* [<= N] */
+} gtf_extract_out;
+
+typedef struct gtf_extract_out_counts {
+    int32_t n_extracted, n_extracted_nodes;
+    int32_t n_remaining, n_remaining_nodes;
+    int32_t n_fragments, n_fragment_nodes;
+} gtf_extract_out_counts;
+
+/* positive for an empty graph, non-decreasing in both arguments */
+size_t gtf_extract_outputs_workspace_bytes(int32_t n_nodes, int32_t n_sub);
+/* Scans only (no atomics); synchronises `stream` once, when *counts is filled. -3 for another
+ * ABI, -2 for a null argument, fragment < 1 or a small workspace, before any launch.
+ * n_nodes == 0: returns 0 with zero counts, nothing launched, nothing written. */
+int gtf_extract_outputs(const gtf_graph* g, const gtf_extract_io* io, int32_t fragment,
+                        const void* extract_workspace, const gtf_extract_out* out, void* workspace,
+                        size_t workspace_bytes, gtf_extract_out_counts* counts, gtf_stream_t stream);
 
 /* ---- Parabolic-model KL training data -------------------------
  * learn_KL_parabolic_model/src/generate_training_data: the per-edge parabolic
