@@ -137,6 +137,25 @@ class GtfEventCsr(ctypes.Structure):
                 ("out_ptr", P), ("out_slot", P), ("n_edges", ctypes.c_int64), ("n_subgraphs", I32), ("pad_", I32)]
 
 
+class GtfEventCols(ctypes.Structure):
+    """gtf_event_cols: the CSV columns of the kept nodes, device arrays in CSV row order"""
+    _fields_ = [("x", P), ("y", P), ("z", P), ("r", P), ("layer_id", P)]
+
+
+class GtfEventOut(ctypes.Structure):
+    """gtf_event_out: the caller-allocated outputs of gtf_event_pack (NULL = not wanted)"""
+    _fields_ = [("gnn", P), ("xyzr", P), ("layer", P), ("node_id", P), ("vivl", P), ("solo", P)]
+
+
+class GtfFillColumn(ctypes.Structure):
+    """gtf_fill_column: one column of gtf_fill_columns"""
+    _fields_ = [("dst", P), ("rows", ctypes.c_int64), ("row_bytes", I32), ("pad_", I32),
+                ("pattern", ctypes.c_uint64)]
+
+
+FILL_MAX_COLUMNS = 32   # GTF_FILL_MAX_COLUMNS
+
+
 class GtfCandidateGraph(ctypes.Structure):
     _fields_ = [("n_nodes", I32), ("n_slots", I32), ("n_edges", I32), ("pad_", I32), ("slot_ptr", P),
                 ("slot_src", P), ("is_edge", P), ("act", P), ("out_ptr", P), ("out_slot", P), ("sub_id", P),
@@ -202,7 +221,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
-           "gtf_subset_gather", "gtf_refresh_send_mw",
+           "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_event_pack", "gtf_fill_columns",
            "gtf_updated_state_pair_counts", "gtf_updated_state_distances", "gtf_set_diagnostics",
            "gtf_device_init", "gtf_malloc", "gtf_free", "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod",
            "gtf_memset", "gtf_stream_synchronize",
@@ -305,6 +324,9 @@ def lib(lean: bool = False):
     L.gtf_graph_subset_apply.argtypes = [G, P, ctypes.POINTER(GtfSubsetOut), P]
     L.gtf_subset_gather.argtypes = [P, I32, ctypes.POINTER(GtfColumn), I32, P]
     L.gtf_refresh_send_mw.argtypes = [G, P, P, P, P]
+    L.gtf_event_pack.argtypes = [ctypes.POINTER(GtfEventCsr), ctypes.POINTER(GtfEventCols),
+                                 ctypes.POINTER(GtfEventOut), P]
+    L.gtf_fill_columns.argtypes = [ctypes.POINTER(GtfFillColumn), I32, P]
     L.gtf_candidate_order.argtypes = [ctypes.POINTER(GtfCandidateGraph), P]
     L.gtf_updated_state_pair_counts.argtypes = [G, N, S, E, P, P]
     L.gtf_updated_state_distances.argtypes = [G, N, S, E, P, P, ctypes.POINTER(GtfPairOut), P]
@@ -342,7 +364,7 @@ def lib(lean: bool = False):
                "gtf_halo_exchange", "gtf_halo_alltoall", "gtf_allreduce_max_i64", "gtf_allgather_bytes",
                "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
                "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
-               "gtf_extract_outputs"):
+               "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -984,6 +984,148 @@ class DeviceGraph:
         c._finish(shape, False)
         return c
 
+    # ------------------------------------------------ event conversion into a resident graph
+    EVENT_FILL = {"has_tse": 1, "is_edge": 1, "rev_edge": 1, "act": 1}   # (else: the field's empty value)
+
+    @classmethod
+    def from_event(cls, ids, x, y, z, r, layer_id, row_a, row_b, device: str = "cuda", mem: str = "torch"):
+        """The packed event of gtf.io.build_event_csr (event_conversion.py:53-101, helper.py:465-545),
+        made in HBM: host columns of the nodes kept by the volume window, in CSV order (io.read_nodes),
+        and the edge rows as io.csr_from_rows takes them (add_edge(row_a, row_b) first). The eight
+        columns go up once; gtf_build_event_csr_device builds the CSR, gtf_event_pack the node columns,
+        gtf_fill_columns the empty states (every edge active, has_tse set) and gtf_graph_prepare the
+        schedules and slot tables. Natural layout, tables == "device"; the node ids are the resident
+        node_id column (node_id_dev, subset) and vivl is ``carried["vivl"]``. host_graph() downloads it."""
+        return cls._from_event(ids, x, y, z, r, layer_id, row_a, row_b, device, mem, lambda part: None)
+
+    @classmethod
+    def _from_event(cls, ids, x, y, z, r, layer_id, row_a, row_b, device, mem, mark):
+        """from_event; mark is called with "upload", "csr", "pack_fill" and "prepare" as each part has
+        been issued (tools/resident_event.py synchronises and reads the clock there)"""
+        if mem not in ("torch", "hip"):
+            raise ValueError("mem must be 'torch' or 'hip'")
+        ids, layer_id, row_a, row_b = (np.ascontiguousarray(a, np.int64).reshape(-1)
+                                       for a in (ids, layer_id, row_a, row_b))
+        x, y, z, r = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (x, y, z, r))
+        N, R = int(ids.size), int(row_a.size)
+        if any(a.size != N for a in (x, y, z, r, layer_id)) or row_b.size != R:
+            raise ValueError("from_event: one x, y, z, r and layer_id per node id, one row_b per row_a")
+        if N and int(layer_id.min()) < 0:
+            raise ValueError("from_event: negative layer_id")
+        c = cls.__new__(cls)
+        c.mem = mem
+        c.torch = torch = _torch() if mem == "torch" else None
+        if torch is not None:
+            c.device = torch.device(device)
+            c.lib = nat.lib()
+        else:
+            c.device = device
+            c.lib = nat.lib(lean=True)
+            nat.check(c.lib.gtf_device_init(int(device.split(":")[1]) if ":" in device else 0))
+        c.layout, c.order, c.slot_perm, c.pad_plan = "natural", None, None, None
+        c.slot_ptr_host, c._node_id_host = None, None
+        c.tables = "device"
+        c.t, c.carried = {}, {}
+        c._event = True   # (host_graph: a whole event, its ids resident -- not a subset() child)
+        L, vp = c.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
+        E = n_sub = 0
+        if N:
+            up = {k: c._dev_from(a) for k, a in (("ids", ids), ("a", row_a), ("b", row_b), ("x", x), ("y", y),
+                                                 ("z", z), ("r", r), ("layer_id", layer_id))}
+            mark("upload")
+            csr = {k: c._dev_empty(n, np.int32) for k, n in (("order", N), ("sub_id", N), ("slot_ptr", N + 1),
+                                                              ("slot_src", 2 * R), ("tse_rank", 2 * R),
+                                                              ("out_ptr", N + 1), ("out_slot", 2 * R))}
+            nb = int(L.gtf_build_event_device_workspace_bytes(N, R))
+            ws = c._dev_empty(nb, np.uint8)
+            ev = nat.GtfEventCsr(N, R, vp(up["ids"]), vp(up["a"]), vp(up["b"]),
+                                 *[vp(csr[k]) for k in ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank",
+                                                        "out_ptr", "out_slot")], 0, 0, 0)
+            nat.check(L.gtf_build_event_csr_device(ctypes.byref(ev), vp(ws), ctypes.c_size_t(nb), c.stream))
+            E, n_sub = int(ev.n_edges), int(ev.n_subgraphs)
+            for k in ("sub_id", "slot_ptr", "out_ptr"):
+                c.t[k] = csr[k]
+            for k in ("slot_src", "tse_rank", "out_slot"):   # trimmed to the edges the builder kept
+                c.t[k] = csr[k][:E] if torch is not None else csr[k].view(0, E, np.int32)
+        else:   # no node in the window: nothing to build
+            for k, n in (("sub_id", 0), ("slot_ptr", 1), ("out_ptr", 1), ("slot_src", 0), ("tse_rank", 0),
+                         ("out_slot", 0)):
+                c.t[k] = c._dev_zeros(n, np.int32)
+        mark("csr")
+        c.n_nodes, c.n_slots, c.n_edges, c.n_sub, c._sub_ok = N, E, E, n_sub, True
+        for f in ("gnn", "xyzr", "layer") + MUTABLE_NODE:
+            dt, shape, _ = NODE_FIELDS[f]
+            c.t[f] = c._dev_empty(N * int(np.prod(shape, dtype=np.int64)), dt)
+        for f, (dt, shape, _) in SLOT_FIELDS.items():
+            if f not in c.t and f != "slot_key":
+                c.t[f] = c._dev_empty(E * int(np.prod(shape, dtype=np.int64)), dt)
+        c.t["node_id"] = c._dev_empty(N, np.int64)
+        c.t["solo"] = c._dev_empty(N, np.uint8)
+        c.carried["vivl"] = c._dev_empty(2 * N, np.float64)
+        if N:
+            cols = nat.GtfEventCols(vp(up["x"]), vp(up["y"]), vp(up["z"]), vp(up["r"]), vp(up["layer_id"]))
+            out = nat.GtfEventOut(c.ptr("gnn"), c.ptr("xyzr"), c.ptr("layer"), c.ptr("node_id"),
+                                  vp(c.carried["vivl"]), c.ptr("solo"))
+            nat.check(L.gtf_event_pack(ctypes.byref(ev), ctypes.byref(cols), ctypes.byref(out), c.stream))
+            for fields, rows, names in ((NODE_FIELDS, N, MUTABLE_NODE),
+                                        (SLOT_FIELDS, E, tuple(f for f in SLOT_FIELDS
+                                                               if f not in ("slot_key", "slot_src", "tse_rank")))):
+                fc = []
+                for f in names:
+                    dt, shape, fill = fields[f]
+                    word = np.full(8 // np.dtype(dt).itemsize, cls.EVENT_FILL.get(f, fill), dtype=dt)
+                    fc.append(nat.GtfFillColumn(c.ptr(f), rows, int(np.prod(shape, dtype=np.int64)) * word.itemsize, 0,
+                                                int(word.view(np.uint64)[0])))
+                if rows:
+                    nat.check(L.gtf_fill_columns((nat.GtfFillColumn * len(fc))(*fc), len(fc), c.stream))
+            # the uploaded columns, the untrimmed CSR arrays and the builder's workspace go out of scope
+            # with kernels in flight: a torch allocation is reused in stream order, a plain one is freed at once
+            if torch is None:
+                nat.check(L.gtf_stream_synchronize(None))
+        mark("pack_fill")
+        shape = TrackGraph(N, E, None, None, np.zeros(E, np.int32), {}, {}, n_sub)   # (sizes only)
+        if N > 0 and E > 0:
+            c._device_tables(shape, None, True)
+        else:   # nothing for gtf_graph_prepare to build: the few tables of a slot-free graph from the host
+            from .graph import empty_arrays
+            zp = np.zeros(N + 1, np.int32)
+            solo = c.t["solo"]
+            c._host_tables(TrackGraph(N, 0, zp, zp, np.zeros(0, np.int32), empty_arrays(NODE_FIELDS, N),
+                                      empty_arrays(SLOT_FIELDS, 0), n_sub), None, True, False)
+            c.t["solo"] = solo
+        c._finish(shape, False)
+        mark("prepare")
+        return c
+
+    def host_graph(self):
+        """A from_event() graph (or, with the states build_event_dev computes, the event network) as a
+        host TrackGraph without a parent: every resident field downloaded, tag = node_id and
+        slot_key = node_id[slot_src] (a fresh event has no orphan keys). Returns (graph, vivl [N, 2]).
+        to_host(parent) stays the way back for a subset() child."""
+        if not getattr(self, "_event", False):
+            raise ValueError("host_graph: this DeviceGraph holds no node_id column (only a graph made by "
+                             "DeviceGraph.from_event() carries its ids and vivl; a subset() child has to_host(parent))")
+        self.materialize()
+        N, S = self.n_nodes, self.n_slots
+        nid = self._np(self.t["node_id"]).astype(np.int64, copy=False)
+        node, slot = {"tag": nid.copy(), "node_id": nid}, {}
+        for f, (dt, shape, _) in NODE_FIELDS.items():
+            if f not in node:
+                node[f] = self._np(self.t[f]).reshape((N,) + shape).astype(dt, copy=False)
+        for f, (dt, shape, _) in SLOT_FIELDS.items():
+            if f != "slot_key":
+                slot[f] = self._np(self.t[f]).reshape((S,) + shape).astype(dt, copy=False)
+        src = slot["slot_src"].astype(np.int64)
+        if (src < 0).any():
+            raise ValueError("host_graph: orphan keys (a subset() child): their ids come from to_host(parent)")
+        slot["slot_key"] = nid[src] if S else np.zeros(0, np.int64)
+        slot["uts_fresh"] = slot["uts_fresh"] & 1   # (bit 1 is cleared by materialize())
+        from .graph import check_layout
+        h = TrackGraph(N, S, self._np(self.t["slot_ptr"]), self._np(self.t["out_ptr"]), self._np(self.t["out_slot"]),
+                       node, slot, self.n_sub)
+        check_layout(h)
+        return h, self._np(self.carried["vivl"]).reshape(N, 2)
+
     def refresh_send_mw(self):
         """gtf.graph.refresh_send_mw on the device (gtf_refresh_send_mw): send_mw of every edge
         from the sender's current tse_mw, NaN where the sender holds no such entry"""

@@ -23,7 +23,9 @@ and its orders come from gtf_build_event_csr (csrc/gtf_build.cpp: the reference'
 node, successor and weakly-connected-component orders and the set order of the
 track_state_estimates keys, helper.py:277,350-351, without networkx); the states,
 priors, mixture weights and degrees are computed on the device
-(gtf_track_state_estimates + gtf_node_ops).
+(gtf_track_state_estimates + gtf_node_ops). :func:`build_event_dev` does the same without
+leaving HBM (gtf_event_pack, gtf_fill_columns) and returns the DeviceGraph that
+``run(d, None, resident="device")`` starts iteration 1 on.
 """
 from __future__ import annotations
 
@@ -109,13 +111,37 @@ def build_event(event_prefix: str, min_volume: int, max_volume: int, p: Params =
     return g, vivl
 
 
+def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Params = None, device="cuda",
+                    mem: str = "torch"):
+    """build_event (event_conversion.py:53-101) without its host round trips: the parsed CSV columns go
+    up once and the packed network, its empty states and its tables are made in HBM
+    (DeviceGraph.from_event: gtf_build_event_csr_device, gtf_event_pack, gtf_fill_columns,
+    gtf_graph_prepare); the states, priors, mixture weights, degrees and send weights are computed on
+    that object. Returns the DeviceGraph: run(d, None, resident="device") starts iteration 1 on it,
+    d.host_graph() downloads what build_event returns."""
+    from . import io
+    from .device import DeviceGraph
+    p = p or Params()
+    ids, x, y, z, r, layer = io.read_nodes(event_prefix + "nodes.csv", min_volume, max_volume)
+    n2, n1 = io.read_edges(event_prefix + "edges.csv")
+    d = DeviceGraph.from_event(ids, x, y, z, r, layer, n1, n2, device, mem)
+    if d.n_nodes == 0:
+        return d
+    d.clear_errors()
+    d.track_state_estimates(p)
+    d.node_ops(["priors_tse", "mw_tse", "degree"], p)
+    d.raise_errors()
+    d.refresh_send_mw()
+    return d
+
+
 def _ids(g: TrackGraph, groups):
     return [g.node["node_id"][np.asarray(x, np.int64)] for x in groups]
 
 
-def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
+def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
         device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host",
-        resident=False) -> List[Iteration]:
+        resident=False, host: TrackGraph = None) -> List[Iteration]:
     """Iterations ``first`` .. ``first + iterations - 1`` of the loop, starting from
     the stage input ``g`` (the event network for iteration 1). Stops early when
     nothing remains. keep_graphs: also return each iteration's stage output and
@@ -136,19 +162,40 @@ def run(g: TrackGraph, vivl, iterations: int = 3, p: Params = None, ex: extract.
     goes to DeviceGraph.subset without leaving HBM, and vivl and node_id travel as carried node
     columns. No download, no host order or outputs, no to_host: per iteration the host receives
     the counts, the candidate / remaining / fragment node-id lists and the p-values (and, with
-    keep_graphs, the graphs it asked for, downloaded after the step). Same Iteration records."""
+    keep_graphs, the graphs it asked for, downloaded after the step). Same Iteration records.
+    g may then be the DeviceGraph of build_event_dev, with vivl=None: iteration ``first`` runs on that
+    object (no upload at all), vivl is its carried column, and keep_graphs takes the host copy it needs
+    from host_graph() -- or from ``host``, where the caller already holds that download (it is
+    modified like a host ``g``). Any other ``resident`` with such an input raises ValueError, and so
+    does ``host`` with a host ``g``."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
     if resident not in (False, True, "device"):
         raise ValueError("resident must be False, True or 'device'")
-    vivl = np.asarray(vivl, np.float64).reshape(-1, 2)
-    if vivl.shape[0] != g.n_nodes:
-        raise ValueError("vivl must have one row per node")
     out = []
     torch = None
     dnext = None   # resident: the DeviceGraph that already holds the iteration's input
     vivl_dev = None   # resident="device": vivl beside it
+    if isinstance(g, DeviceGraph):
+        # a resident event (build_event_dev): iteration `first` runs on the object itself
+        if resident != "device":
+            raise ValueError("a DeviceGraph input needs resident='device' (the other modes start from a host graph)")
+        if vivl is not None:
+            raise ValueError("a DeviceGraph input carries its own vivl (carried['vivl']): pass vivl=None")
+        if "node_id" not in g.t or "vivl" not in getattr(g, "carried", {}):
+            raise ValueError("a DeviceGraph input must hold the node_id and vivl columns (DeviceGraph.from_event)")
+        dnext, vivl_dev = g, g.carried["vivl"]
+        if host is not None and (host.n_nodes, host.n_slots) != (g.n_nodes, g.n_slots):
+            raise ValueError("host must be the DeviceGraph input's own host_graph()")
+        # (only the saved graphs need a host copy)
+        g = (host if host is not None else dnext.host_graph()[0]) if keep_graphs else None
+    else:
+        if host is not None:
+            raise ValueError("host goes with a DeviceGraph input only")
+        vivl = np.asarray(vivl, np.float64).reshape(-1, 2)
+        if vivl.shape[0] != g.n_nodes:
+            raise ValueError("vivl must have one row per node")
     for it in range(first, first + iterations):
         if (dnext.n_nodes if resident == "device" and dnext is not None else g.n_nodes) == 0:
             break

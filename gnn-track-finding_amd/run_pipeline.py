@@ -17,6 +17,9 @@ Layout under ROOTDIR (the run script's directories, one file each):
     metrics.json                             with --truth: reconstruction efficiency and purities
                                              (gtf.metrics; the run script's last step, :143-146)
 
+--resident / --resident-outputs keep the graph between iterations on the GPU; --resident-event also
+builds the event there (pipeline.build_event_dev) and starts iteration 1 on that object. Same files.
+
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
 """
@@ -63,11 +66,16 @@ def main(argv=None):
     ap.add_argument("--resident-outputs", action="store_true",
                     help="as --resident, and the candidate order and the stage outputs are computed on the GPU too "
                          "(pipeline.run(resident='device')): only the id lists and p-values come back")
+    ap.add_argument("--resident-event", action="store_true",
+                    help="as --resident-outputs, and event conversion builds the event in GPU memory "
+                         "(pipeline.build_event_dev): iteration 1 starts on that object; only with --start 1")
     ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
     if args.start < 1 or args.end < args.start:
         ap.error("need 1 <= start <= end")
+    if args.resident_event and args.start != 1:
+        ap.error("--resident-event converts the event: only with --start 1")
     p = Params(sigma0xy=args.sigma0xy, sigma0rz=args.sigma0rz, sigma0rz2=args.sigma0rz2,
                endcap_boundary=args.endcapboundary, chi2_cut=args.chi2)
     ex = extract.Params(args.pval, args.numhits, args.separation, args.merge, args.sigma0xy, args.sigma0rz,
@@ -78,8 +86,12 @@ def main(argv=None):
         if not args.eventNetwork:
             ap.error("-n is required when starting at iteration 1")
         t0 = time.perf_counter()
-        g, vivl = pipeline.build_event(os.path.join(args.eventNetwork, "event_1_filtered_graph_"), args.min_volume,
-                                       args.max_volume, p, args.device)
+        prefix = os.path.join(args.eventNetwork, "event_1_filtered_graph_")
+        if args.resident_event:
+            dev = pipeline.build_event_dev(prefix, args.min_volume, args.max_volume, p, args.device)
+            g, vivl = dev.host_graph()   # (the saved file; the loop starts on the resident object)
+        else:
+            g, vivl = pipeline.build_event(prefix, args.min_volume, args.max_volume, p, args.device)
         times["event_conversion"] = time.perf_counter() - t0
         store.save_graph(os.path.join(_dir(root, "track_sim", "network"), "graph.npz"), g, vivl)
         print("event conversion: %d nodes, %d directed edges, %d subgraphs (%.3f s)"
@@ -88,8 +100,12 @@ def main(argv=None):
         g, vivl = store.load_graph(os.path.join(root, "iteration_%d" % (args.start - 1), "remaining", "graph.npz"))
         if vivl is None:
             raise SystemExit("remaining graph has no vivl array")
-    its = pipeline.run(g, vivl, args.end - args.start + 1, p, ex, args.device, first=args.start, keep_graphs=True,
-                       resident="device" if args.resident_outputs else args.resident)
+    if args.resident_event and g.n_nodes:
+        its = pipeline.run(dev, None, args.end - args.start + 1, p, ex, args.device, first=1, keep_graphs=True,
+                           resident="device", host=g)   # (the download above: no second one)
+    else:
+        its = pipeline.run(g, vivl, args.end - args.start + 1, p, ex, args.device, first=args.start, keep_graphs=True,
+                           resident="device" if args.resident_outputs or args.resident_event else args.resident)
     for it in its:
         d = os.path.join(root, "iteration_%d" % it.index)
         store.save_graph(os.path.join(_dir(d, "network"), "graph.npz"), it.network)

@@ -812,6 +812,83 @@ int gtf_build_event_csr(gtf_event_csr* ev);
 size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows);
 int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
 
+/* ---- event conversion: the packed event's columns and empty states, on the GPU --------
+ * What is left of event conversion between the CSR above and gtf_track_state_estimates:
+ * the node attributes construct_graph stores (helper.py:465-545: GNN_Measurement, xyzr,
+ * in_volume_layer_id, vivl_id) in packed node order, and the arrays of an event that holds
+ * no state yet (event_conversion.py:53-101: every edge activated, every node with an empty
+ * track_state_estimates dict) -- array for array gtf/io.py build_event_csr. gtf_event.hip.
+ *
+ * A C caller's sequence from CSV columns to iteration 1: upload the columns,
+ * gtf_build_event_csr_device, allocate at the returned n_edges, gtf_event_pack,
+ * gtf_fill_columns (once per axis), gtf_graph_prepare, gtf_track_state_estimates,
+ * gtf_node_ops (priors_tse, mw_tse, degree), gtf_refresh_send_mw. */
+
+/* gtf_event_cols: the CSV columns of the kept nodes (helper.py:524-531), DEVICE arrays in
+ * CSV row order -- the rows ev->node_id names. r stays an input: the reference computes it
+ * with the C library's pow (helper.py:12-13; gtf/io.py edge_length_xy), which is the CSV
+ * reader's business. layer_id must be >= 0 (the volume window's lower bound). */
+typedef struct gtf_event_cols {
+    const double* x;           /* [n_nodes] */
+    const double* y;           /* [n_nodes] */
+    const double* z;           /* [n_nodes] */
+    const double* r;           /* [n_nodes] */
+    const int64_t* layer_id;   /* [n_nodes] */
+} gtf_event_cols;
+
+/* gtf_event_out: the node attributes of helper.py:465-545 as DEVICE arrays in packed node
+ * order (N = ev->n_nodes), caller-allocated; NULL = not wanted. */
+typedef struct gtf_event_out {
+    double*  gnn;       /* [N*4] (x, y, z, r)[order]: gtf_graph.gnn */
+    double*  xyzr;      /* [N*4] the same bits, a separate array: gtf_graph.xyzr */
+    double*  layer;     /* [N]   (double)(layer_id % 100): gtf_graph.layer */
+    int64_t* node_id;   /* [N]   ev->node_id[order] */
+    double*  vivl;      /* [N*2] (layer_id / 1000, layer_id % 100), integer division: gtf_extract_io.vivl */
+    uint8_t* solo;      /* [N]   1 = alone in its subgraph: gtf_graph.solo */
+} gtf_event_out;
+
+/* After gtf_build_event_csr_device on the same device *ev (event_conversion.py:53-101,
+ * helper.py:465-545): reads ev->n_nodes, order, node_id and sub_id (non-decreasing in packed
+ * order, as the builder leaves it: solo compares the two neighbouring entries) and the
+ * columns of *in; writes the wanted arrays of *out on `stream`, one launch. A value of
+ * `order` outside [0, n_nodes) reads nothing (NaN / -1 rows). Does not synchronise, does not
+ * allocate. n_nodes == 0, or no output wanted: returns 0, nothing launched.
+ * -2, decided on the host before any device work: a NULL ev or out, negative sizes, more
+ * than INT32_MAX / 4 nodes, a missing event array or input column that a wanted output
+ * reads (the message names it): order for every output but solo, node_id for node_id,
+ * sub_id for solo (which reads nothing else, so solo alone needs neither order nor *in),
+ * x, y, z, r for gnn / xyzr, layer_id for layer / vivl.
+ * The values of layer_id lie in device memory and are NOT checked, neither on the host nor
+ * in the kernel: a negative one gives C's truncating / and %, not the floor division of the
+ * NumPy path, so the caller refuses it when it reads the CSV (as DeviceGraph.from_event does). */
+int gtf_event_pack(const gtf_event_csr* ev, const gtf_event_cols* in, const gtf_event_out* out, gtf_stream_t stream);
+
+#define GTF_FILL_MAX_COLUMNS 32
+
+/* One column of gtf_fill_columns (an attribute no node or edge of event_conversion.py:53-101
+ * holds yet): `rows` rows of row_bytes each at dst, every word of which -- the row itself
+ * for 1 and 4 bytes, 8-byte words otherwise -- gets the low bytes of `pattern`. */
+typedef struct gtf_fill_column {
+    void* dst;           /* device, aligned to the word (1, 4 or 8 bytes); may be NULL with rows == 0 */
+    int64_t rows;        /* >= 0 */
+    int32_t row_bytes;   /* 1, 4 or a multiple of 8 */
+    int32_t pad_;
+    uint64_t pattern;    /* e.g. 0x7ff8000000000000 (NaN), 0xffffffff (int32 -1), 0xff (int8 -1), 0, 1 */
+} gtf_fill_column;
+
+/* The initial value of every other array of a fresh event (event_conversion.py:53-101 starts
+ * from nodes without state dicts; gtf/graph.py empty_arrays, gtf/io.py build_event_csr), the
+ * counterpart of gtf_subset_gather's column table: `cols` is a HOST array of at most
+ * GTF_FILL_MAX_COLUMNS columns, which travels in the kernel arguments, one launch. One call
+ * per axis initialises a gtf_nodes / gtf_states / gtf_edges set: NaN in the float arrays,
+ * -1 in uts_rank, uts_side and degree, 0 in has_merged, has_uts and the fresh flags, 1 in
+ * has_tse, is_edge, rev_edge and act. Does not synchronise, does not allocate. n_cols == 0,
+ * or no column with rows: returns 0, nothing launched.
+ * -2, decided on the host before any device work: n_cols outside [0, 32], negative rows, a
+ * row_bytes that is neither 1, 4 nor a multiple of 8, a NULL dst with rows > 0, a dst not
+ * aligned to its words. */
+int gtf_fill_columns(const gtf_fill_column* cols, int32_t n_cols, gtf_stream_t stream);
+
 /* ---- graph preparation: the optional fields of gtf_graph, built on the GPU -----------
  * The schedules and graph-static slot tables that the lane-group kernels read (every
  * optional field of gtf_graph up to v8 except the packed schedule and the padded tiles),
