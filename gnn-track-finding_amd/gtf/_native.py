@@ -131,6 +131,37 @@ class GtfExtractOutCounts(ctypes.Structure):
                 ("n_fragments", I32), ("n_fragment_nodes", I32)]
 
 
+class GtfTruth(ctypes.Structure):
+    """gtf_truth: the event's truth tables on the device; keyword construction only --
+    struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_nodes", I32), ("n_entries", I32),
+                ("n_particles", I32), ("pad_", I32), ("node_id", P), ("node_ptr", P), ("node_part", P),
+                ("part_id", P), ("part_hits", P), ("part_ref", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfTruth)
+        self.abi_version = ABI_VERSION
+
+
+class GtfScoreState(ctypes.Structure):
+    """gtf_score_state: the per-particle claims the scoring calls accumulate"""
+    _fields_ = [("n_particles", I32), ("pad_", I32), ("best_key", P), ("best_good", P), ("best_total", P),
+                ("error", P)]
+
+
+class GtfScoreOut(ctypes.Structure):
+    """gtf_score_out: optional per-candidate results of gtf_score_candidates (NULL = not wanted)"""
+    _fields_ = [("pid", P), ("n_good", P), ("total", P), ("passes", P)]
+
+
+class GtfScoreCounts(ctypes.Structure):
+    _fields_ = [("n_reconstructed", I32), ("error", U32)]
+
+
+SCORE_ERR_MISSING, SCORE_ERR_WORKSPACE, SCORE_ERR_RANGE = 1, 2, 4   # GTF_SCORE_ERR_*
+
+
 class GtfEventCsr(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int64), ("n_rows", ctypes.c_int64), ("node_id", P), ("row_a", P),
                 ("row_b", P), ("order", P), ("sub_id", P), ("slot_ptr", P), ("slot_src", P), ("tse_rank", P),
@@ -218,6 +249,8 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
            "gtf_subgraph_ptr_device", "gtf_candidate_order_workspace_bytes", "gtf_candidate_order_device",
            "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
+           "gtf_score_reset", "gtf_score_workspace_bytes", "gtf_score_candidates",
+           "gtf_score_finish_workspace_bytes", "gtf_score_finish",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
@@ -297,6 +330,14 @@ def lib(lean: bool = False):
     L.gtf_extract_outputs_workspace_bytes.argtypes = [I32, I32]
     L.gtf_extract_outputs.argtypes = [G, ctypes.POINTER(GtfExtractIO), I32, P, ctypes.POINTER(GtfExtractOut), P,
                                       ctypes.c_size_t, ctypes.POINTER(GtfExtractOutCounts), P]
+    TR, SS = ctypes.POINTER(GtfTruth), ctypes.POINTER(GtfScoreState)
+    L.gtf_score_reset.argtypes = [SS, P]
+    L.gtf_score_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_score_workspace_bytes.argtypes = [I32, I32]
+    L.gtf_score_candidates.argtypes = [TR, P, P, I32, I32, ctypes.POINTER(GtfScoreOut), SS, P, ctypes.c_size_t, P]
+    L.gtf_score_finish_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_score_finish_workspace_bytes.argtypes = [I32]
+    L.gtf_score_finish.argtypes = [TR, SS, P, P, P, P, P, ctypes.POINTER(GtfScoreCounts), P, ctypes.c_size_t, P]
     SH = ctypes.POINTER(GtfShard)
     L.gtf_pass_shard.argtypes = [G, N, S, S, E, PR, SH, P, P, ctypes.POINTER(P)]
     L.gtf_tag_sweep_shard.argtypes = [G, P, P, P, P, SH, I32, I32, P]
@@ -364,7 +405,8 @@ def lib(lean: bool = False):
                "gtf_halo_exchange", "gtf_halo_alltoall", "gtf_allreduce_max_i64", "gtf_allgather_bytes",
                "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
                "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
-               "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns"):
+               "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
+               "gtf_score_candidates", "gtf_score_finish"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -169,12 +169,19 @@ def _groups(ptr, members):
     return [members[ptr[i]:ptr[i + 1]] for i in range(len(ptr) - 1)]
 
 
-def outputs_dev(d, res, fragment, ids=True):
+def outputs_dev(d, res, fragment, ids=True, lists=True):
     """outputs() on the device (gtf_extract_outputs) from run_dev's result, which must not have
     been reused since. Returns the dict outputs() returns -- the lists as host arrays: of node
     ids (int64) with ids=True, of node indices with ids=False -- plus "keep", the device uint8
     [N] mask DeviceGraph.subset takes, and "left" [n_sub] on the device. Only the counts, the
-    pointers, the p-values and the lists asked for cross to the host."""
+    pointers, the p-values and the lists asked for cross to the host.
+    lists=False: no list crosses and no Python group is built. The dict then carries the device
+    arrays as gtf_extract_outputs wrote them, at their upper-bound sizes -- "cand_ptr", "rem_ptr",
+    "frag_ptr" (int32), "cand_ids", "rem_ids", "frag_ids" (int64 node ids; "cand_members",
+    "rem_nodes", "frag_nodes", int32 indices, with ids=False), "pval_xy", "pval_zr" -- and
+    "counts", the six host counts that say how much of each is filled (n_extracted,
+    n_extracted_nodes, n_remaining, n_remaining_nodes, n_fragments, n_fragment_nodes): what
+    metrics.DeviceScorer.add and DeviceGraph.subset consume without a host copy."""
     N, n1, S = d.n_nodes, max(d.n_nodes, 1), d.n_sub
     o = {"left": d._dev_empty(max(S, 1), np.int32), "keep": d._dev_empty(n1, np.uint8),
          "pval_xy": d._dev_empty(n1, np.float64), "pval_zr": d._dev_empty(n1, np.float64)}
@@ -182,30 +189,46 @@ def outputs_dev(d, res, fragment, ids=True):
         o[k + "_ptr"] = d._dev_empty(n1 + 1, np.int32)
         o[k + "_list"] = d._dev_empty(n1, np.int64 if ids else np.int32)
     z = ctypes.c_void_p(0)
-    lists = [_vp(o[k + "_list"]) for k in ("cand", "rem", "frag")]
-    out = nat.GtfExtractOut(_vp(o["left"]), _vp(o["keep"]), _vp(o["cand_ptr"]), z if ids else lists[0],
-                            _vp(o["pval_xy"]), _vp(o["pval_zr"]), _vp(o["rem_ptr"]), z if ids else lists[1],
-                            _vp(o["frag_ptr"]), z if ids else lists[2], _vp(d.node_id_dev()) if ids else z,
-                            *(lists if ids else (z, z, z)))
+    lp = [_vp(o[k + "_list"]) for k in ("cand", "rem", "frag")]
+    out = nat.GtfExtractOut(_vp(o["left"]), _vp(o["keep"]), _vp(o["cand_ptr"]), z if ids else lp[0],
+                            _vp(o["pval_xy"]), _vp(o["pval_zr"]), _vp(o["rem_ptr"]), z if ids else lp[1],
+                            _vp(o["frag_ptr"]), z if ids else lp[2], _vp(d.node_id_dev()) if ids else z,
+                            *(lp if ids else (z, z, z)))
     nb = int(d.lib.gtf_extract_outputs_workspace_bytes(N, S))
     ws = d._dev_empty(nb, np.uint8)
     cnt = nat.GtfExtractOutCounts()
     nat.check(d.lib.gtf_extract_outputs(ctypes.byref(d.cg), ctypes.byref(res["io"]), int(fragment), _vp(res["ws"]),
                                         ctypes.byref(out), _vp(ws), ctypes.c_size_t(nb), ctypes.byref(cnt),
                                         d.stream))
+    r = {"keep": o["keep"], "left": o["left"], "pval_xy": o["pval_xy"], "pval_zr": o["pval_zr"]}
+    for k in ("cand", "rem", "frag"):
+        r[k + "_ptr"], r[_LIST_KEYS[k][0 if ids else 1]] = o[k + "_ptr"], o[k + "_list"]
+    r["counts"] = {f: int(getattr(cnt, f)) for f, _ in nat.GtfExtractOutCounts._fields_}
+    return outputs_host(d, r) if lists else r
+
+
+_LIST_KEYS = {"cand": ("cand_ids", "cand_members"), "rem": ("rem_ids", "rem_nodes"), "frag": ("frag_ids", "frag_nodes")}
+
+
+def outputs_host(d, r):
+    """the dict outputs_dev(lists=True) returns from the one outputs_dev(lists=False) returned:
+    the filled part of every list and of the p-values copied to the host, the lists cut into
+    one array per group"""
+    c = r["counts"]
 
     def host(t, n):   # the first n elements on the host
         if n == 0:
             return np.empty(0, t.dtype if d.torch is None else t.cpu().numpy().dtype)
         return d._np(t[:n] if d.torch is not None else t.view(0, n, t.dtype))
 
-    r = {"keep": o["keep"], "left": o["left"]}
-    for k, key, n, m in (("cand", "extracted", cnt.n_extracted, cnt.n_extracted_nodes),
-                         ("rem", "remaining", cnt.n_remaining, cnt.n_remaining_nodes),
-                         ("frag", "fragments", cnt.n_fragments, cnt.n_fragment_nodes)):
-        r[key] = _groups(host(o[k + "_ptr"], n + 1), host(o[k + "_list"], m)) if N else []
-    r["pval_xy"], r["pval_zr"] = host(o["pval_xy"], cnt.n_extracted), host(o["pval_zr"], cnt.n_extracted)
-    return r
+    h = {"keep": r["keep"], "left": r["left"]}
+    for k, key, n, m in (("cand", "extracted", c["n_extracted"], c["n_extracted_nodes"]),
+                         ("rem", "remaining", c["n_remaining"], c["n_remaining_nodes"]),
+                         ("frag", "fragments", c["n_fragments"], c["n_fragment_nodes"])):
+        lst = r[_LIST_KEYS[k][0]] if _LIST_KEYS[k][0] in r else r[_LIST_KEYS[k][1]]
+        h[key] = _groups(host(r[k + "_ptr"], n + 1), host(lst, m)) if d.n_nodes else []
+    h["pval_xy"], h["pval_zr"] = host(r["pval_xy"], c["n_extracted"]), host(r["pval_zr"], c["n_extracted"])
+    return h
 
 
 def candidate_order(g: TrackGraph) -> np.ndarray:

@@ -19,11 +19,19 @@ Reference flow (reconstruction_efficiency.py):
   * efficiency = reconstructed * 100 / reference tracks, printed with 3 decimals (:213).
 
 A node's hit_dissociation is construct_graph's (helper.py:466-479): the node's unique
-hit ids in mapping-row order and each hit's particle id. Integer counting over ~10^3
-candidates: host-side NumPy, no kernel.
+hit ids in mapping-row order and each hit's particle id.
+
+Two paths, the same numbers. :func:`reconstruction_efficiency` is host-side NumPy over
+candidate lists: integer counting, enough for the ~10^3 candidates of one volume.
+:class:`DeviceScorer` scores the resident loop's candidates where they are: the device
+arrays of gtf_extract_outputs go into gtf_score_candidates (csrc/gtf_score.hip), once per
+iteration, against the event's static tables (:func:`truth_tables`) uploaded once, and
+gtf_score_finish returns the matched particles in match order; no candidate list crosses
+to the host.
 """
 from __future__ import annotations
 
+import ctypes
 import dataclasses
 from typing import Dict, Optional, Sequence
 
@@ -199,6 +207,179 @@ def reconstruction_efficiency(cand_ptr, cand_ids, m: HitMapping, particle_id, px
     matched = np.zeros(n_cand, bool)
     matched[first] = True
     return Result(int(first.size), int(ref_ids.size), tpur[first], ppur[first], pid, n_good, matched)
+
+
+@dataclasses.dataclass
+class TruthTables:
+    """gtf_truth's arrays on the host (include/gtf.h), and the number of reference tracks"""
+    node_id: np.ndarray      # [T] int64 ascending
+    node_ptr: np.ndarray     # [T+1] int32
+    node_part: np.ndarray    # [P] int64: node_particles' CSR
+    part_id: np.ndarray      # [R] int64 ascending: the region particles
+    part_hits: np.ndarray    # [R] int32: hits in the region (= reference hits, see reference_tracks)
+    part_ref: np.ndarray     # [R] uint8: 1 = reference track
+    n_reference: int
+
+
+def truth_tables(m: HitMapping, particle_id, px, py, min_volume: int, max_volume: int, truth_hit_id=None,
+                 truth_particle_id=None) -> TruthTables:
+    """The event's static tables for the device scorer, from region_hits, reference_tracks
+    (:41-91) and node_particles (helper.py:466-479) as reconstruction_efficiency uses them."""
+    th = m.hit_id if truth_hit_id is None else truth_hit_id
+    tpid = m.particle_id if truth_particle_id is None else truth_particle_id
+    rows = region_hits(m, th, tpid, high_pt_particles(particle_id, px, py), min_volume, max_volume)
+    ref_ids, _, (reg_ids, reg_hits) = reference_tracks(m, rows)
+    nid, nptr, npart = node_particles(m, truth_hit_id, truth_particle_id)
+    if npart.size > np.iinfo(np.int32).max:
+        raise ValueError("more than 2^31 - 1 hit_dissociation entries")
+    return TruthTables(nid.astype(np.int64), nptr.astype(np.int32), npart.astype(np.int64), reg_ids.astype(np.int64),
+                       reg_hits.astype(np.int32), np.isin(reg_ids, ref_ids).astype(np.uint8), int(ref_ids.size))
+
+
+class DeviceScorer:
+    """reconstruction_efficiency on the device (gtf_score_*, include/gtf.h): the tables go up
+    once; add() scores one iteration's candidates from the device arrays gtf_extract_outputs
+    wrote (extract.outputs_dev(lists=False): "cand_ptr", "cand_ids") and result() returns the
+    Result the host function returns for the same candidates concatenated by ascending group.
+    The reference reads iterations last, ..., 1 (score(cumulative=True)) while the loop
+    produces 1, ..., last: pass group = last - iteration; the calls may come in any order and
+    need distinct groups. mem "torch" (torch tensors, the stream torch is on) or "hip"
+    (gtf.devmem, the default stream), as DeviceGraph."""
+
+    def __init__(self, tables: TruthTables, device="cuda", mem: str = "torch"):
+        from . import _native as nat
+        if mem not in ("torch", "hip"):
+            raise ValueError("mem must be 'torch' or 'hip'")
+        self.nat, self.tables, self.mem = nat, tables, mem
+        if mem == "torch":
+            import torch
+            self.torch, self.device, self.lib = torch, torch.device(device), nat.lib()
+        else:
+            self.torch, self.device, self.lib = None, device, nat.lib(lean=True)
+            nat.check(self.lib.gtf_device_init(int(str(device).split(":")[1]) if ":" in str(device) else 0))
+        t = tables
+        self.R = int(t.part_id.size)
+        self._dev = [self._from(a) for a in (t.node_id, t.node_ptr, t.node_part, t.part_id, t.part_hits, t.part_ref)]
+        self.truth = nat.GtfTruth(n_nodes=int(t.node_id.size), n_entries=int(t.node_part.size), n_particles=self.R,
+                                  **{k: self._p(a) for k, a in zip(("node_id", "node_ptr", "node_part", "part_id",
+                                                                    "part_hits", "part_ref"), self._dev)})
+        r1 = max(self.R, 1)
+        self._state = [self._empty(r1, np.uint64), self._empty(r1, np.int32), self._empty(r1, np.int32),
+                       self._empty(1, np.uint32)]
+        self.state = nat.GtfScoreState(self.R, 0, *(self._p(a) for a in self._state))
+        self.reset()
+
+    # -- this scorer's allocator (DeviceGraph's two, without a graph)
+    def _empty(self, n, dtype):
+        if self.torch is None:
+            from .devmem import HipArray
+            return HipArray(n, dtype)
+        dt = np.dtype(dtype)
+        # (torch has no unsigned 64-bit arithmetic; the bytes are what the library reads)
+        name = {"uint64": "int64", "uint32": "int32"}.get(dt.name, dt.name)
+        return self.torch.empty(n, dtype=getattr(self.torch, name), device=self.device)
+
+    def _from(self, a):
+        a = np.ascontiguousarray(a).reshape(-1)
+        if self.torch is None:
+            from .devmem import HipArray
+            return HipArray.from_numpy(a)
+        return self.torch.from_numpy(a).to(self.device)
+
+    def _host(self, t, n, dtype):
+        """the first n elements as a host array of dtype (synchronises)"""
+        if n == 0:
+            return np.empty(0, dtype)
+        a = t.view(0, n, t.dtype).numpy() if self.torch is None else t[:n].cpu().numpy()
+        return a.view(dtype)
+
+    @staticmethod
+    def _p(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+
+    @property
+    def stream(self):
+        if self.torch is None:
+            return ctypes.c_void_p(0)
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        """forget every candidate scored so far (does not synchronise)"""
+        self.nat.check(self.lib.gtf_score_reset(ctypes.byref(self.state), self.stream))
+        self._per = []        # (group, n_cand, pid, n_good) device arrays of the per_candidate adds
+        self._all_per = True
+        self._keep = []       # mem "hip": the adds' workspaces, which a plain allocation would free at once
+
+    def add(self, cand_ptr_dev, cand_ids_dev, n_cand: int, group: int, per_candidate: bool = False,
+            n_members: Optional[int] = None):
+        """Score n_cand candidates: cand_ptr_dev [n_cand + 1] int32 and cand_ids_dev int64 device
+        arrays (gtf_extract_out's form). n_members: the host count of members when the caller has
+        it (gtf_extract_out_counts.n_extracted_nodes), else the length of cand_ids_dev sizes the
+        workspace. Nothing synchronises."""
+        nat = self.nat
+        n_cand, group = int(n_cand), int(group)
+        if n_cand == 0:
+            if per_candidate:
+                self._per.append((group, 0, None, None))
+            else:
+                self._all_per = False
+            return
+        if not cand_ids_dev.numel():      # (candidates without a member: the library still wants an array)
+            cand_ids_dev = self._empty(1, np.int64)
+        cap = int(cand_ids_dev.numel()) if n_members is None else int(n_members)
+        nb = int(self.lib.gtf_score_workspace_bytes(n_cand, cap))
+        ws = self._empty(nb, np.uint8)
+        out = nat.GtfScoreOut()
+        if per_candidate:
+            pid, good = self._empty(n_cand, np.int64), self._empty(n_cand, np.int32)
+            out = nat.GtfScoreOut(self._p(pid), self._p(good), None, None)
+            self._per.append((group, n_cand, pid, good))
+        else:
+            self._all_per = False
+        nat.check(self.lib.gtf_score_candidates(ctypes.byref(self.truth), self._p(cand_ptr_dev), self._p(cand_ids_dev),
+                                                n_cand, group, ctypes.byref(out), ctypes.byref(self.state),
+                                                self._p(ws), ctypes.c_size_t(nb), self.stream))
+        if self.torch is None:
+            self._keep.append(ws)      # (until result() has synchronised)
+
+    def result(self) -> Result:
+        """The Result of everything added since the last reset (synchronises once). The purities
+        are formed here, in fp64, from the integer records. reconstructed_pid / n_good / matched
+        are filled when every add asked for per_candidate, concatenated by ascending group;
+        else they are empty."""
+        nat = self.nat
+        r1 = max(self.R, 1)
+        key, pid = self._empty(r1, np.uint64), self._empty(r1, np.int64)
+        good, total, hits = (self._empty(r1, np.int32) for _ in range(3))
+        nb = int(self.lib.gtf_score_finish_workspace_bytes(self.R))
+        ws = self._empty(nb, np.uint8)
+        cnt = nat.GtfScoreCounts()
+        rc = self.lib.gtf_score_finish(ctypes.byref(self.truth), ctypes.byref(self.state), self._p(key), self._p(pid),
+                                       self._p(good), self._p(total), self._p(hits), ctypes.byref(cnt), self._p(ws),
+                                       ctypes.c_size_t(nb), self.stream)
+        self._keep = []
+        if rc == -2 and cnt.error & nat.SCORE_ERR_MISSING:
+            raise ValueError("a candidate node has no hit_dissociation")
+        nat.check(rc)
+        n = int(cnt.n_reconstructed)
+        g = self._host(good, n, np.int32) * 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tpur = g / self._host(total, n, np.int32)
+            ppur = g / self._host(hits, n, np.int32)
+        if self._all_per and self._per:
+            per = sorted(self._per, key=lambda x: x[0])
+            start, at = {}, 0
+            for grp, nc, _, _ in per:
+                start[grp] = at
+                at += nc
+            rp = np.concatenate([self._host(p, nc, np.int64) for _, nc, p, _ in per])
+            ng = np.concatenate([self._host(q, nc, np.int32) for _, nc, _, q in per]).astype(np.int64)
+            matched = np.zeros(at, bool)
+            k = self._host(key, n, np.uint64)
+            matched[[start[int(x >> np.uint64(32))] + int(x & np.uint64(0xffffffff)) for x in k]] = True
+        else:
+            rp, ng, matched = np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, bool)
+        return Result(n, self.tables.n_reference, tpur, ppur, rp, ng, matched)
 
 
 def summary(r: Result) -> Dict[str, object]:

@@ -49,15 +49,16 @@ class Iteration:
     fragments/ directories and candidates/pvals.csv)."""
     index: int
     stage: str
-    candidates: List[np.ndarray]
+    candidates: Optional[List[np.ndarray]]      # (the three lists: None from run(lists=False))
     pval_xy: np.ndarray
     pval_zr: np.ndarray
-    remaining: List[np.ndarray]
-    fragments: List[np.ndarray]
+    remaining: Optional[List[np.ndarray]]
+    fragments: Optional[List[np.ndarray]]
     seconds: dict
     network: Optional[TrackGraph] = None      # the stage's output graph (keep_graphs=True)
     remaining_graph: Optional[TrackGraph] = None    # next iteration's input
     remaining_vivl: Optional[np.ndarray] = None
+    counts: Optional[dict] = None             # resident="device": gtf_extract_out_counts' six counts
 
 
 def event_layout(event_prefix: str, min_volume: int, max_volume: int, builder: str = "native", device="cuda"):
@@ -141,7 +142,7 @@ def _ids(g: TrackGraph, groups):
 
 def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,
         device="cuda", first: int = 1, keep_graphs: bool = False, tables: str = "host",
-        resident=False, host: TrackGraph = None) -> List[Iteration]:
+        resident=False, host: TrackGraph = None, scorer=None, lists: bool = True) -> List[Iteration]:
     """Iterations ``first`` .. ``first + iterations - 1`` of the loop, starting from
     the stage input ``g`` (the event network for iteration 1). Stops early when
     nothing remains. keep_graphs: also return each iteration's stage output and
@@ -167,12 +168,21 @@ def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = Non
     object (no upload at all), vivl is its carried column, and keep_graphs takes the host copy it needs
     from host_graph() -- or from ``host``, where the caller already holds that download (it is
     modified like a host ``g``). Any other ``resident`` with such an input raises ValueError, and so
-    does ``host`` with a host ``g``."""
+    does ``host`` with a host ``g``.
+    scorer, lists (resident="device" only; anything else raises ValueError): scorer, a
+    metrics.DeviceScorer, receives every iteration's candidates as the device arrays of
+    gtf_extract_outputs -- scorer.add(cand_ptr, cand_ids, n, group) with group = (first +
+    iterations - 1) - it, so its result() is reconstruction_efficiency over the candidates of the
+    iterations last, ..., first, as the reference reads them. lists=False: no node-id list crosses to
+    the host; the records' candidates / remaining / fragments are None, their p-values stay, and
+    ``counts`` holds the six counts (it does with lists=True as well)."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
     if resident not in (False, True, "device"):
         raise ValueError("resident must be False, True or 'device'")
+    if resident != "device" and (scorer is not None or not lists):
+        raise ValueError("scorer and lists=False need resident='device' (the other modes build the lists on the host)")
     out = []
     torch = None
     dnext = None   # resident: the DeviceGraph that already holds the iteration's input
@@ -222,7 +232,16 @@ def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = Non
             order = extract.candidate_order_dev(d)
             res = extract.run_dev(d, vivl_dev, ex, order)
             t2 = time.perf_counter()
-            o = extract.outputs_dev(d, res, ex.numhits, ids=True)
+            o = extract.outputs_dev(d, res, ex.numhits, ids=True, lists=False)
+            counts = o["counts"]
+            if scorer is not None:
+                scorer.add(o["cand_ptr"], o["cand_ids"], counts["n_extracted"], (first + iterations - 1) - it,
+                           n_members=counts["n_extracted_nodes"])
+            if lists:
+                o = extract.outputs_host(d, o)
+            else:   # (the p-values are per candidate, not lists of node ids: they come back)
+                o = dict(o, extracted=None, remaining=None, fragments=None,
+                         **{k: d._np(o[k][:counts["n_extracted"]]) for k in ("pval_xy", "pval_zr")})
             dnext = d.subset(o["keep"], gnn=res["gnn"], carry={"vivl": vivl_dev})
             dnext.refresh_send_mw()
             if it % 2 == 0 and dnext.n_nodes:      # remove_state_metadata.py, as below
@@ -231,7 +250,7 @@ def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = Non
                 dnext.raise_errors()
             t3 = time.perf_counter()
             rec = Iteration(it, stage, o["extracted"], o["pval_xy"], o["pval_zr"], o["remaining"], o["fragments"],
-                            {"stage": t1 - t0, "extract": t2 - t1, "next": t3 - t2})
+                            {"stage": t1 - t0, "extract": t2 - t1, "next": t3 - t2}, counts=counts)
             vivl_dev = dnext.carried["vivl"]
             if keep_graphs:
                 # after the step (it left d's arrays as the stage wrote them). As the other modes:

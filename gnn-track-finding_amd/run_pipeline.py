@@ -19,6 +19,9 @@ Layout under ROOTDIR (the run script's directories, one file each):
 
 --resident / --resident-outputs keep the graph between iterations on the GPU; --resident-event also
 builds the event there (pipeline.build_event_dev) and starts iteration 1 on that object. Same files.
+--resident-metrics (implies --resident-outputs) scores the candidates on the GPU as well: with --truth,
+metrics.json comes from gtf.metrics.DeviceScorer, fed each iteration's candidates where
+gtf_extract_outputs left them, instead of from the saved lists. The same values.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -41,6 +44,39 @@ def _dir(*parts):
     d = os.path.join(*parts)
     os.makedirs(d, exist_ok=True)
     return d
+
+
+class _Scorers:
+    """what pipeline.run(scorer=...) feeds: one DeviceScorer over every iteration ("cumulative") and
+    one that holds the latest iteration only ("last_iteration", as the run script leaves the
+    directory): it is reset before each add"""
+
+    def __init__(self, tables, device):
+        from gtf import metrics
+        self.cumulative = metrics.DeviceScorer(tables, device)
+        self.last = metrics.DeviceScorer(tables, device)
+
+    def add(self, cand_ptr, cand_ids, n_cand, group, **kw):
+        self.cumulative.add(cand_ptr, cand_ids, n_cand, group, **kw)
+        self.last.reset()
+        self.last.add(cand_ptr, cand_ids, n_cand, 0, **kw)
+
+
+def _scorers(args):
+    """the truth files as reconstruction_efficiency.score reads them -> the two device scorers"""
+    import numpy as np
+    import pandas as pd
+    from gtf import metrics
+    pre = os.path.join(args.truth, "event000001000-")
+    particles = pd.read_csv(pre + "particles.csv")
+    m = metrics.HitMapping.from_frame(pd.read_csv(pre + args.mapping))
+    th = tp = None
+    if os.path.isfile(pre + "truth.csv"):
+        truth = pd.read_csv(pre + "truth.csv", usecols=["hit_id", "particle_id"])
+        th, tp = truth.hit_id.to_numpy(np.int64), truth.particle_id.to_numpy(np.int64)
+    tables = metrics.truth_tables(m, particles.particle_id.to_numpy(), particles.px.to_numpy(),
+                                  particles.py.to_numpy(), args.min_volume, args.max_volume, th, tp)
+    return _Scorers(tables, args.device)
 
 
 def main(argv=None):
@@ -69,6 +105,9 @@ def main(argv=None):
     ap.add_argument("--resident-event", action="store_true",
                     help="as --resident-outputs, and event conversion builds the event in GPU memory "
                          "(pipeline.build_event_dev): iteration 1 starts on that object; only with --start 1")
+    ap.add_argument("--resident-metrics", action="store_true",
+                    help="as --resident-outputs, and with --truth the candidates are scored on the GPU "
+                         "(gtf.metrics.DeviceScorer) from the extraction's device arrays; only with --start 1")
     ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
@@ -76,6 +115,8 @@ def main(argv=None):
         ap.error("need 1 <= start <= end")
     if args.resident_event and args.start != 1:
         ap.error("--resident-event converts the event: only with --start 1")
+    if args.resident_metrics and args.start != 1:
+        ap.error("--resident-metrics scores the iterations of this run: only with --start 1")
     p = Params(sigma0xy=args.sigma0xy, sigma0rz=args.sigma0rz, sigma0rz2=args.sigma0rz2,
                endcap_boundary=args.endcapboundary, chi2_cut=args.chi2)
     ex = extract.Params(args.pval, args.numhits, args.separation, args.merge, args.sigma0xy, args.sigma0rz,
@@ -100,12 +141,15 @@ def main(argv=None):
         g, vivl = store.load_graph(os.path.join(root, "iteration_%d" % (args.start - 1), "remaining", "graph.npz"))
         if vivl is None:
             raise SystemExit("remaining graph has no vivl array")
+    scorers = _scorers(args) if args.resident_metrics and args.truth else None
+    extra = {"scorer": scorers} if scorers else {}
     if args.resident_event and g.n_nodes:
         its = pipeline.run(dev, None, args.end - args.start + 1, p, ex, args.device, first=1, keep_graphs=True,
-                           resident="device", host=g)   # (the download above: no second one)
+                           resident="device", host=g, **extra)   # (the download above: no second one)
     else:
+        on_dev = args.resident_outputs or args.resident_event or args.resident_metrics
         its = pipeline.run(g, vivl, args.end - args.start + 1, p, ex, args.device, first=args.start, keep_graphs=True,
-                           resident="device" if args.resident_outputs or args.resident_event else args.resident)
+                           resident="device" if on_dev else args.resident, **extra)
     for it in its:
         d = os.path.join(root, "iteration_%d" % it.index)
         store.save_graph(os.path.join(_dir(d, "network"), "graph.npz"), it.network)
@@ -128,7 +172,10 @@ def main(argv=None):
         from gtf import metrics
         res = {}
         for name, cum in (("last_iteration", False), ("cumulative", True)):
-            r = re_cli.score(args.truth, root, args.min_volume, args.max_volume, its[-1].index, args.mapping, cum)
+            if scorers:
+                r = (scorers.cumulative if cum else scorers.last).result()
+            else:
+                r = re_cli.score(args.truth, root, args.min_volume, args.max_volume, its[-1].index, args.mapping, cum)
             res[name] = metrics.summary(r)
             print("%s: %d / %d reference tracks reconstructed, efficiency %s %%"
                   % (name, r.n_reconstructed, r.n_reference, r.efficiency_str))

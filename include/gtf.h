@@ -30,6 +30,9 @@
  *                       serial subgraph loop src/extrapolate/extrapolate_merged_states.py:406-451
  *   gtf_updated_state_distances -> calculate_distance_between_updated_states/
  *                       calculate_distance_between_updated_track_states.py:27-104,134-195
+ *   gtf_score_reset, gtf_score_candidates, gtf_score_finish
+ *                    -> src/extract/reconstruction_efficiency.py:118-183 (the candidates'
+ *                       majority particles, the three tests, the match order and its counts)
  */
 #ifndef GTF_H
 #define GTF_H
@@ -662,6 +665,131 @@ size_t gtf_extract_outputs_workspace_bytes(int32_t n_nodes, int32_t n_sub);
 int gtf_extract_outputs(const gtf_graph* g, const gtf_extract_io* io, int32_t fragment,
                         const void* extract_workspace, const gtf_extract_out* out, void* workspace,
                         size_t workspace_bytes, gtf_extract_out_counts* counts, gtf_stream_t stream);
+
+/* ---- Candidate scoring: reconstruction efficiency and purities ---------------------
+ * src/extract/reconstruction_efficiency.py:118-183 (gtf/metrics.py majority and
+ * reconstruction_efficiency) on the device arrays gtf_extract_outputs leaves: cand_ptr /
+ * cand_ids go straight into gtf_score_candidates, once per iteration, and gtf_score_finish
+ * returns the matched particles in the script's match order. Everything is integer; the
+ * caller forms the purities n_good / total and n_good / hits in fp64, so they are the
+ * host's divisions bit for bit. gtf_score.hip.
+ *
+ * The three tests of :150-163 in integers: n_good >= 0.5 * hits, n_good / total >= 0.5 and
+ * n_good / hits >= 0.5 are 2 n_good >= hits and 2 n_good >= total, because 0.5 and every
+ * count here (< 2^31) are exact in fp64, 0.5 * hits is exact, and a correctly rounded
+ * quotient n / t is monotone in the real quotient with 0.5 representable: n / t >= 0.5 in
+ * fp64 exactly when n / t >= 1/2 in the rationals. (t == 0 gives NaN there and never passes:
+ * an empty candidate never passes here.)
+ *
+ * gtf_truth: the event's static truth tables, DEVICE arrays built once per event by the
+ * caller (gtf/metrics.py truth_tables: reconstruction_efficiency.py:41-91 the reference
+ * tracks, helper.py:466-479 hit_dissociation). reference_tracks returns the same count array
+ * for a particle's "reference hits" and its "region hits" (nhits[good] and nhits of one
+ * np.unique), so ONE count per particle, part_hits, serves both thresholds. Particle ids
+ * are arbitrary int64 (0 = noise occurs); both id arrays ascend as signed int64. */
+typedef struct gtf_truth {
+    uint32_t struct_size;       /* sizeof(gtf_truth) as the caller compiled it */
+    uint32_t abi_version;       /* GTF_ABI_VERSION */
+    int32_t n_nodes;            /* T: nodes with a hit_dissociation */
+    int32_t n_entries;          /* P: particle entries of all of them */
+    int32_t n_particles;        /* R: region particles */
+    int32_t pad_;
+    const int64_t* node_id;     /* [T]   ascending, distinct */
+    const int32_t* node_ptr;    /* [T+1] CSR over node_part */
+    const int64_t* node_part;   /* [P]   the particle of each hit of the node, in the node's hit order */
+    const int64_t* part_id;     /* [R]   ascending, distinct */
+    const int32_t* part_hits;   /* [R]   the particle's hits in the region (= its reference hits) */
+    const uint8_t* part_ref;    /* [R]   1 = reference track */
+} gtf_truth;
+
+/* gtf_score_state: what the calls accumulate, DEVICE arrays owned by the caller. */
+typedef struct gtf_score_state {
+    int32_t n_particles;        /* R of the gtf_truth it is used with */
+    int32_t pad_;
+    uint64_t* best_key;         /* [R] (group << 32) | candidate index of the claim; all-ones = none */
+    int32_t* best_good;         /* [R] n_good of the claiming candidate */
+    int32_t* best_total;        /* [R] its number of particle entries */
+    uint32_t* error;            /* [1] GTF_SCORE_ERR_* */
+} gtf_score_state;
+
+#define GTF_SCORE_ERR_MISSING   1u   /* a member id with no row in node_id */
+#define GTF_SCORE_ERR_WORKSPACE 2u   /* cand_ptr[n_cand] members do not fit the workspace given */
+#define GTF_SCORE_ERR_RANGE     4u   /* a candidate of 2^31 or more particle entries, or a decreasing cand_ptr */
+
+/* Optional per-candidate results of gtf_score_candidates (gtf/metrics.py majority,
+ * reconstruction_efficiency.py:132-134), DEVICE arrays [n_cand]; NULL = not wanted. */
+typedef struct gtf_score_out {
+    int64_t* pid;               /* the most frequent particle id, ties to the id seen first; 0 when empty */
+    int32_t* n_good;            /* its count */
+    int32_t* total;             /* the candidate's particle entries */
+    uint8_t* passes;            /* 1 = reference track and both thresholds (before "first one wins") */
+} gtf_score_out;
+
+typedef struct gtf_score_counts {
+    int32_t n_reconstructed;
+    uint32_t error;             /* the state's error word */
+} gtf_score_counts;
+
+/* reconstruction_efficiency.py:118-121 (the empty tallies): every key all-ones, the error word
+ * cleared. Two stream-ordered fills; does not synchronise. -2 for a null state or array. */
+int gtf_score_reset(const gtf_score_state* state, gtf_stream_t stream);
+
+/* Scratch of one gtf_score_candidates call (reconstruction_efficiency.py:125-134) over n_cand
+ * candidates of n_members members in all (gtf_extract_out_counts: n_extracted,
+ * n_extracted_nodes). Positive for zero sizes, non-decreasing in each argument (negative
+ * counts as 0), depends on nothing else: no buffer is sized by the number of particle
+ * entries, which has no bound the host knows (members need not be distinct). */
+size_t gtf_score_workspace_bytes(int32_t n_cand, int32_t n_members);
+
+/* reconstruction_efficiency.py:125-163 (gtf/metrics.py candidate_particles, majority and the
+ * three tests of reconstruction_efficiency) for the candidates cand_ptr [n_cand + 1] (int32) /
+ * cand_ids (int64 node ids), device arrays in gtf_extract_out's form; n_cand the host count
+ * gtf_extract_outputs returned. The number of members is cand_ptr[n_cand], on the device: the
+ * call takes the largest n_members with gtf_score_workspace_bytes(n_cand, n_members) <=
+ * workspace_bytes as its capacity and sets GTF_SCORE_ERR_WORKSPACE (reading nothing past it)
+ * when there are more.
+ *   Per candidate, over the concatenation of its members' node_part rows (members in list
+ * order, hits in node order): pid = the most frequent id, ties to the id whose first
+ * occurrence comes first (Counter + max(key=get), :132-134), n_good its count, total the
+ * number of entries; an empty candidate gives 0 / 0 / 0. It passes when pid is in part_id
+ * with part_ref set, 2 n_good >= part_hits and 2 n_good >= total (:150-163, see above). A
+ * passing candidate claims its particle with the key (group << 32) | index by a 64-bit
+ * atomic minimum on that particle's own word, and in a second launch the candidate whose key
+ * is the stored one writes best_good / best_total: its only writer. The smallest key wins, so
+ * inside a call the first passing candidate (:166-171) and across calls the smallest group,
+ * in whatever order the calls come: the reference reads iterations last, ..., 1 while the loop
+ * produces 1, ..., last, so the caller passes group = last - iteration. Calls on one state
+ * need distinct groups.
+ *   Three launches and one hipCUB exclusive sum: the members' rows (a binary search each),
+ * the vote (a 16-lane group per candidate of up to 16 entries, the wavefront for up to 64,
+ * a whole-wave loop that is slow but correct for any length beyond), the winners. No atomic
+ * on a shared word: the claims go to per-particle words and the error word is touched only
+ * on a violation. Nothing is allocated, nothing synchronises. n_cand == 0: returns 0,
+ * nothing launched. -3 for another ABI of *truth; -2 for a null truth / state / array that is
+ * needed, negative sizes or group, state->n_particles != truth->n_particles, or a workspace
+ * below gtf_score_workspace_bytes(n_cand, 0): all decided on the host before any launch. */
+int gtf_score_candidates(const gtf_truth* truth, const int32_t* cand_ptr, const int64_t* cand_ids,
+                         int32_t n_cand, int32_t group, const gtf_score_out* out,
+                         const gtf_score_state* state, void* workspace, size_t workspace_bytes,
+                         gtf_stream_t stream);
+
+/* Scratch of gtf_score_finish (reconstruction_efficiency.py:166-171) for R region particles:
+ * positive for 0, non-decreasing. */
+size_t gtf_score_finish_workspace_bytes(int32_t n_particles);
+
+/* reconstruction_efficiency.py:166-171, :213 (gtf/metrics.py: the match order of
+ * reconstruction_efficiency): the matched particles, compacted and sorted by key (one hipCUB
+ * radix sort of the R keys; the all-ones keys of the unmatched sort behind them), written as
+ * n_reconstructed records in match order -- the order :166-171 appends the purities in:
+ * out_key (the winning candidate's group and index), out_pid, out_good, out_total and
+ * out_hits = part_hits, DEVICE arrays [R], NULL = not wanted. Synchronises `stream` once to
+ * fill *counts. Returns -2 with "a candidate node has no hit_dissociation" when the error word
+ * holds GTF_SCORE_ERR_MISSING (the reference's KeyError), -2 with their own messages for the
+ * other two bits; -3 / -2 on the host before any launch as gtf_score_candidates. */
+int gtf_score_finish(const gtf_truth* truth, const gtf_score_state* state, uint64_t* out_key,
+                     int64_t* out_pid, int32_t* out_good, int32_t* out_total, int32_t* out_hits,
+                     gtf_score_counts* counts, void* workspace, size_t workspace_bytes,
+                     gtf_stream_t stream);
 
 /* ---- Parabolic-model KL training data -------------------------
  * learn_KL_parabolic_model/src/generate_training_data: the per-edge parabolic
