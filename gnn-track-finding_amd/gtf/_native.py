@@ -162,6 +162,36 @@ class GtfScoreCounts(ctypes.Structure):
 SCORE_ERR_MISSING, SCORE_ERR_WORKSPACE, SCORE_ERR_RANGE = 1, 2, 4   # GTF_SCORE_ERR_*
 
 
+class GtfTruthIn(ctypes.Structure):
+    """gtf_truth_in: the parsed columns gtf_truth_build reads, device arrays; keyword construction
+    only -- struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_rows", I32), ("n_truth", I32),
+                ("n_particles", I32), ("num_layers", I32), ("min_volume", I32), ("max_volume", I32),
+                ("pt_cut", F64), ("node_idx", P), ("hit_id", P), ("particle_id", P), ("volume_id", P),
+                ("layer_id", P), ("module_id", P), ("truth_hit", P), ("truth_part", P), ("part_id", P),
+                ("px", P), ("py", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfTruthIn)
+        self.abi_version = ABI_VERSION
+
+
+class GtfTruthBuf(ctypes.Structure):
+    """gtf_truth_buf: the caller-allocated outputs of gtf_truth_build, each at its bound n_rows (+ 1)"""
+    _fields_ = [("node_id", P), ("node_ptr", P), ("node_part", P), ("part_id", P), ("part_hits", P),
+                ("part_ref", P)]
+
+
+class GtfTruthCounts(ctypes.Structure):
+    _fields_ = [("n_nodes", I32), ("n_entries", I32), ("n_particles", I32), ("n_reference", I32),
+                ("error", U32), ("pad_", I32)]
+
+
+TRUTH_ERR_MISSING, TRUTH_ERR_RANGE = 1, 2   # GTF_TRUTH_ERR_*
+TRUTH_ID_LIMIT = 1 << 21                    # volume_id, layer_id, module_id: [0, 2^21)
+
+
 class GtfEventCsr(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int64), ("n_rows", ctypes.c_int64), ("node_id", P), ("row_a", P),
                 ("row_b", P), ("order", P), ("sub_id", P), ("slot_ptr", P), ("slot_src", P), ("tse_rank", P),
@@ -251,6 +281,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
            "gtf_score_reset", "gtf_score_workspace_bytes", "gtf_score_candidates",
            "gtf_score_finish_workspace_bytes", "gtf_score_finish",
+           "gtf_truth_build_workspace_bytes", "gtf_truth_build",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
@@ -338,6 +369,10 @@ def lib(lean: bool = False):
     L.gtf_score_finish_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_score_finish_workspace_bytes.argtypes = [I32]
     L.gtf_score_finish.argtypes = [TR, SS, P, P, P, P, P, ctypes.POINTER(GtfScoreCounts), P, ctypes.c_size_t, P]
+    L.gtf_truth_build_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_truth_build_workspace_bytes.argtypes = [I32, I32, I32]
+    L.gtf_truth_build.argtypes = [ctypes.POINTER(GtfTruthIn), ctypes.POINTER(GtfTruthBuf), TR,
+                                  ctypes.POINTER(GtfTruthCounts), P, ctypes.c_size_t, P]
     SH = ctypes.POINTER(GtfShard)
     L.gtf_pass_shard.argtypes = [G, N, S, S, E, PR, SH, P, P, ctypes.POINTER(P)]
     L.gtf_tag_sweep_shard.argtypes = [G, P, P, P, P, SH, I32, I32, P]
@@ -406,7 +441,7 @@ def lib(lean: bool = False):
                "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
                "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
                "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
-               "gtf_score_candidates", "gtf_score_finish"):
+               "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -27,7 +27,8 @@ candidate lists: integer counting, enough for the ~10^3 candidates of one volume
 arrays of gtf_extract_outputs go into gtf_score_candidates (csrc/gtf_score.hip), once per
 iteration, against the event's static tables (:func:`truth_tables`) uploaded once, and
 gtf_score_finish returns the matched particles in match order; no candidate list crosses
-to the host.
+to the host. :func:`truth_tables_dev` builds those tables on the device as well
+(gtf_truth_build, csrc/gtf_truth.hip), from the columns uploaded once: the same arrays.
 """
 from __future__ import annotations
 
@@ -236,41 +237,23 @@ def truth_tables(m: HitMapping, particle_id, px, py, min_volume: int, max_volume
                        reg_hits.astype(np.int32), np.isin(reg_ids, ref_ids).astype(np.uint8), int(ref_ids.size))
 
 
-class DeviceScorer:
-    """reconstruction_efficiency on the device (gtf_score_*, include/gtf.h): the tables go up
-    once; add() scores one iteration's candidates from the device arrays gtf_extract_outputs
-    wrote (extract.outputs_dev(lists=False): "cand_ptr", "cand_ids") and result() returns the
-    Result the host function returns for the same candidates concatenated by ascending group.
-    The reference reads iterations last, ..., 1 (score(cumulative=True)) while the loop
-    produces 1, ..., last: pass group = last - iteration; the calls may come in any order and
-    need distinct groups. mem "torch" (torch tensors, the stream torch is on) or "hip"
-    (gtf.devmem, the default stream), as DeviceGraph."""
+class _Mem:
+    """the two allocators of the device paths here (DeviceGraph's two, without a graph): "torch"
+    (torch tensors, the stream torch is on) or "hip" (gtf.devmem, the default stream)"""
 
-    def __init__(self, tables: TruthTables, device="cuda", mem: str = "torch"):
+    def __init__(self, device="cuda", mem: str = "torch"):
         from . import _native as nat
         if mem not in ("torch", "hip"):
             raise ValueError("mem must be 'torch' or 'hip'")
-        self.nat, self.tables, self.mem = nat, tables, mem
+        self.nat, self.mem = nat, mem
         if mem == "torch":
             import torch
             self.torch, self.device, self.lib = torch, torch.device(device), nat.lib()
         else:
             self.torch, self.device, self.lib = None, device, nat.lib(lean=True)
             nat.check(self.lib.gtf_device_init(int(str(device).split(":")[1]) if ":" in str(device) else 0))
-        t = tables
-        self.R = int(t.part_id.size)
-        self._dev = [self._from(a) for a in (t.node_id, t.node_ptr, t.node_part, t.part_id, t.part_hits, t.part_ref)]
-        self.truth = nat.GtfTruth(n_nodes=int(t.node_id.size), n_entries=int(t.node_part.size), n_particles=self.R,
-                                  **{k: self._p(a) for k, a in zip(("node_id", "node_ptr", "node_part", "part_id",
-                                                                    "part_hits", "part_ref"), self._dev)})
-        r1 = max(self.R, 1)
-        self._state = [self._empty(r1, np.uint64), self._empty(r1, np.int32), self._empty(r1, np.int32),
-                       self._empty(1, np.uint32)]
-        self.state = nat.GtfScoreState(self.R, 0, *(self._p(a) for a in self._state))
-        self.reset()
 
-    # -- this scorer's allocator (DeviceGraph's two, without a graph)
-    def _empty(self, n, dtype):
+    def empty(self, n, dtype):
         if self.torch is None:
             from .devmem import HipArray
             return HipArray(n, dtype)
@@ -279,22 +262,26 @@ class DeviceScorer:
         name = {"uint64": "int64", "uint32": "int32"}.get(dt.name, dt.name)
         return self.torch.empty(n, dtype=getattr(self.torch, name), device=self.device)
 
-    def _from(self, a):
+    def from_host(self, a):
         a = np.ascontiguousarray(a).reshape(-1)
         if self.torch is None:
             from .devmem import HipArray
             return HipArray.from_numpy(a)
         return self.torch.from_numpy(a).to(self.device)
 
-    def _host(self, t, n, dtype):
+    def first(self, t, n):
+        """the first n elements of a device array, as a view"""
+        return t.view(0, n, t.dtype) if self.torch is None else t[:n]
+
+    def host(self, t, n, dtype):
         """the first n elements as a host array of dtype (synchronises)"""
         if n == 0:
             return np.empty(0, dtype)
-        a = t.view(0, n, t.dtype).numpy() if self.torch is None else t[:n].cpu().numpy()
+        a = self.first(t, n).numpy() if self.torch is None else t[:n].cpu().numpy()
         return a.view(dtype)
 
     @staticmethod
-    def _p(t):
+    def p(t):
         return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
     @property
@@ -302,6 +289,135 @@ class DeviceScorer:
         if self.torch is None:
             return ctypes.c_void_p(0)
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+
+_TABLE_FIELDS = (("node_id", np.int64), ("node_ptr", np.int32), ("node_part", np.int64), ("part_id", np.int64),
+                 ("part_hits", np.int32), ("part_ref", np.uint8))
+
+
+class DeviceTruth:
+    """truth_tables_dev's result: the six arrays of TruthTables on the device, trimmed views of the
+    buffers gtf_truth_build filled, the number of reference tracks and the GtfTruth struct that
+    gtf_score_candidates takes. host() downloads them as a TruthTables."""
+
+    def __init__(self, mem: _Mem, arrays, truth, counts):
+        self._m, self.truth, self.device, self.mem = mem, truth, mem.device, mem.mem
+        self.n_nodes, self.n_entries = int(counts.n_nodes), int(counts.n_entries)
+        self.n_particles, self.n_reference = int(counts.n_particles), int(counts.n_reference)
+        sizes = (self.n_nodes, self.n_nodes + 1, self.n_entries, self.n_particles, self.n_particles, self.n_particles)
+        self._buffers = arrays      # (the views point into them)
+        for (name, _), a, n in zip(_TABLE_FIELDS, arrays, sizes):
+            setattr(self, name, mem.first(a, n))
+
+    def host(self) -> "TruthTables":
+        """the tables as metrics.truth_tables returns them (synchronises)"""
+        return TruthTables(*(self._m.host(getattr(self, name), getattr(self, name).numel(), dt)
+                             for name, dt in _TABLE_FIELDS), self.n_reference)
+
+
+def truth_tables_dev(m: HitMapping, particle_id, px, py, min_volume: int, max_volume: int, truth_hit_id=None,
+                     truth_particle_id=None, device="cuda", mem: str = "torch") -> DeviceTruth:
+    """truth_tables on the device (gtf_truth_build, csrc/gtf_truth.hip): the columns go up once
+    and the six arrays stay there, array_equal to the host function's. The mapping's volume_id,
+    layer_id and module_id must lie in [0, 2^21) (ValueError); a mapped hit without a truth row
+    is the host's ValueError."""
+    from . import _native as nat
+    mm = _Mem(device, mem)
+    cols = [np.ascontiguousarray(getattr(m, c), np.int64).reshape(-1) for c in
+            ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id")]
+    n = int(cols[0].size)
+    if any(c.size != n for c in cols):
+        raise ValueError("mapping columns of different lengths")
+    truth = []
+    if truth_hit_id is not None:
+        truth = [np.ascontiguousarray(a, np.int64).reshape(-1) for a in (truth_hit_id, truth_particle_id)]
+        if truth[0].size != truth[1].size:
+            raise ValueError("truth columns of different lengths")
+        if truth[0].size == 0:      # (for the library n_truth == 0 means "the mapping's own columns")
+            if n:
+                raise ValueError("a mapped hit has no truth row (helper.__get_particle_id .item())")
+            truth = []
+    part = [np.ascontiguousarray(particle_id, np.int64).reshape(-1), np.ascontiguousarray(px, np.float64).reshape(-1),
+            np.ascontiguousarray(py, np.float64).reshape(-1)]
+    if not part[0].size == part[1].size == part[2].size:
+        raise ValueError("particle columns of different lengths")
+    n_truth, n_part = int(truth[0].size) if truth else 0, int(part[0].size)
+    if min_volume > max_volume:
+        raise ValueError("min_volume > max_volume")
+    if max(n, n_truth, n_part) > 1 << 30:
+        raise ValueError("more than 2^30 rows")
+    dev = [mm.from_host(a) if a.size else None for a in cols + truth + part]
+    d_truth = dev[6:8] if truth else [None, None]
+    names = ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id", "truth_hit", "truth_part",
+             "part_id", "px", "py")
+    tin = nat.GtfTruthIn(n_rows=n, n_truth=n_truth, n_particles=n_part, num_layers=NUM_DISTINCT_LAYERS,
+                         min_volume=int(min_volume), max_volume=int(max_volume), pt_cut=PT_CUT,
+                         **{k: mm.p(a) for k, a in zip(names, dev[:6] + d_truth + dev[-3:])})
+    out = [mm.empty(max(n, 1) + (name == "node_ptr"), dt) for name, dt in _TABLE_FIELDS]
+    buf = nat.GtfTruthBuf(*(mm.p(a) for a in out))
+    nb = int(mm.lib.gtf_truth_build_workspace_bytes(n, n_truth, n_part))
+    ws = mm.empty(nb, np.uint8)
+    t, cnt = nat.GtfTruth(), nat.GtfTruthCounts()
+    rc = mm.lib.gtf_truth_build(ctypes.byref(tin), ctypes.byref(buf), ctypes.byref(t), ctypes.byref(cnt), mm.p(ws),
+                                ctypes.c_size_t(nb), mm.stream)
+    if rc == -2 and cnt.error & nat.TRUTH_ERR_RANGE:
+        raise ValueError("a volume_id, layer_id or module_id outside [0, %d): the device builder packs them "
+                         "into one key (use metrics.truth_tables)" % nat.TRUTH_ID_LIMIT)
+    if rc == -2 and cnt.error & nat.TRUTH_ERR_MISSING:
+        raise ValueError("a mapped hit has no truth row (helper.__get_particle_id .item())")
+    nat.check(rc)
+    return DeviceTruth(mm, out, t, cnt)
+
+
+class DeviceScorer:
+    """reconstruction_efficiency on the device (gtf_score_*, include/gtf.h): the tables go up
+    once; add() scores one iteration's candidates from the device arrays gtf_extract_outputs
+    wrote (extract.outputs_dev(lists=False): "cand_ptr", "cand_ids") and result() returns the
+    Result the host function returns for the same candidates concatenated by ascending group.
+    The reference reads iterations last, ..., 1 (score(cumulative=True)) while the loop
+    produces 1, ..., last: pass group = last - iteration; the calls may come in any order and
+    need distinct groups. mem "torch" (torch tensors, the stream torch is on) or "hip"
+    (gtf.devmem, the default stream), as DeviceGraph. `tables` may be a DeviceTruth
+    (truth_tables_dev): its arrays are used where they are, with its device and allocator."""
+
+    def __init__(self, tables, device="cuda", mem: str = "torch"):
+        on_dev = isinstance(tables, DeviceTruth)
+        m = tables._m if on_dev else _Mem(device, mem)
+        self._m, self.nat, self.tables, self.mem = m, m.nat, tables, m.mem
+        self.torch, self.device, self.lib = m.torch, m.device, m.lib
+        t = tables
+        if on_dev:
+            self.R, self.truth = t.n_particles, t.truth
+        else:
+            self.R = int(t.part_id.size)
+            self._dev = [self._from(a) for a in (t.node_id, t.node_ptr, t.node_part, t.part_id, t.part_hits, t.part_ref)]
+            self.truth = self.nat.GtfTruth(n_nodes=int(t.node_id.size), n_entries=int(t.node_part.size),
+                                           n_particles=self.R,
+                                           **{k: self._p(a) for k, a in zip(("node_id", "node_ptr", "node_part", "part_id",
+                                                                             "part_hits", "part_ref"), self._dev)})
+        nat = self.nat
+        r1 = max(self.R, 1)
+        self._state = [self._empty(r1, np.uint64), self._empty(r1, np.int32), self._empty(r1, np.int32),
+                       self._empty(1, np.uint32)]
+        self.state = nat.GtfScoreState(self.R, 0, *(self._p(a) for a in self._state))
+        self.reset()
+
+    # -- this scorer's allocator
+    def _empty(self, n, dtype):
+        return self._m.empty(n, dtype)
+
+    def _from(self, a):
+        return self._m.from_host(a)
+
+    def _host(self, t, n, dtype):
+        """the first n elements as a host array of dtype (synchronises)"""
+        return self._m.host(t, n, dtype)
+
+    _p = staticmethod(_Mem.p)
+
+    @property
+    def stream(self):
+        return self._m.stream
 
     def reset(self):
         """forget every candidate scored so far (does not synchronise)"""

@@ -22,6 +22,8 @@ builds the event there (pipeline.build_event_dev) and starts iteration 1 on that
 --resident-metrics (implies --resident-outputs) scores the candidates on the GPU as well: with --truth,
 metrics.json comes from gtf.metrics.DeviceScorer, fed each iteration's candidates where
 gtf_extract_outputs left them, instead of from the saved lists. The same values.
+--resident-truth (implies --resident-metrics) also builds the scorer's truth tables on the GPU
+(gtf.metrics.truth_tables_dev) from the parsed truth files. The same metrics.json, byte for byte.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -74,8 +76,12 @@ def _scorers(args):
     if os.path.isfile(pre + "truth.csv"):
         truth = pd.read_csv(pre + "truth.csv", usecols=["hit_id", "particle_id"])
         th, tp = truth.hit_id.to_numpy(np.int64), truth.particle_id.to_numpy(np.int64)
-    tables = metrics.truth_tables(m, particles.particle_id.to_numpy(), particles.px.to_numpy(),
-                                  particles.py.to_numpy(), args.min_volume, args.max_volume, th, tp)
+    cols = (m, particles.particle_id.to_numpy(), particles.px.to_numpy(), particles.py.to_numpy(), args.min_volume,
+            args.max_volume, th, tp)
+    if args.resident_truth:
+        tables = metrics.truth_tables_dev(*cols, device=args.device)
+    else:
+        tables = metrics.truth_tables(*cols)
     return _Scorers(tables, args.device)
 
 
@@ -108,6 +114,9 @@ def main(argv=None):
     ap.add_argument("--resident-metrics", action="store_true",
                     help="as --resident-outputs, and with --truth the candidates are scored on the GPU "
                          "(gtf.metrics.DeviceScorer) from the extraction's device arrays; only with --start 1")
+    ap.add_argument("--resident-truth", action="store_true",
+                    help="as --resident-metrics, and the scorer's truth tables are built on the GPU too "
+                         "(gtf.metrics.truth_tables_dev); only with --start 1")
     ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
@@ -115,6 +124,8 @@ def main(argv=None):
         ap.error("need 1 <= start <= end")
     if args.resident_event and args.start != 1:
         ap.error("--resident-event converts the event: only with --start 1")
+    if args.resident_truth:
+        args.resident_metrics = True
     if args.resident_metrics and args.start != 1:
         ap.error("--resident-metrics scores the iterations of this run: only with --start 1")
     p = Params(sigma0xy=args.sigma0xy, sigma0rz=args.sigma0rz, sigma0rz2=args.sigma0rz2,

@@ -33,6 +33,8 @@
  *   gtf_score_reset, gtf_score_candidates, gtf_score_finish
  *                    -> src/extract/reconstruction_efficiency.py:118-183 (the candidates'
  *                       majority particles, the three tests, the match order and its counts)
+ *   gtf_truth_build  -> src/extract/reconstruction_efficiency.py:41-91 (the reference tracks) and
+ *                       utilities/helper.py:466-479 (hit_dissociation): the scorer's static tables
  */
 #ifndef GTF_H
 #define GTF_H
@@ -681,9 +683,10 @@ int gtf_extract_outputs(const gtf_graph* g, const gtf_extract_io* io, int32_t fr
  * fp64 exactly when n / t >= 1/2 in the rationals. (t == 0 gives NaN there and never passes:
  * an empty candidate never passes here.)
  *
- * gtf_truth: the event's static truth tables, DEVICE arrays built once per event by the
- * caller (gtf/metrics.py truth_tables: reconstruction_efficiency.py:41-91 the reference
- * tracks, helper.py:466-479 hit_dissociation). reference_tracks returns the same count array
+ * gtf_truth: the event's static truth tables, DEVICE arrays built once per event: by
+ * gtf_truth_build below from the parsed columns on the device, or by the caller on the host
+ * and uploaded (gtf/metrics.py truth_tables: reconstruction_efficiency.py:41-91 the reference
+ * tracks, helper.py:466-479 hit_dissociation; the definition of both). reference_tracks returns the same count array
  * for a particle's "reference hits" and its "region hits" (nhits[good] and nhits of one
  * np.unique), so ONE count per particle, part_hits, serves both thresholds. Particle ids
  * are arbitrary int64 (0 = noise occurs); both id arrays ascend as signed int64. */
@@ -790,6 +793,91 @@ int gtf_score_finish(const gtf_truth* truth, const gtf_score_state* state, uint6
                      int64_t* out_pid, int32_t* out_good, int32_t* out_total, int32_t* out_hits,
                      gtf_score_counts* counts, void* workspace, size_t workspace_bytes,
                      gtf_stream_t stream);
+
+/* ---- The truth tables themselves: gtf_truth_build ---------------------------------
+ * gtf/metrics.py truth_tables (reconstruction_efficiency.py:41-91, helper.py:466-479) on the
+ * device: from the parsed columns of the hit mapping, the truth file and the particles file,
+ * DEVICE arrays in file row order, to the six arrays of a gtf_truth, array_equal to the host
+ * function's. gtf_truth.hip.
+ *
+ * Limits. volume_id, layer_id and module_id of every mapping row must lie in [0, 2^21) (they
+ * are packed into one sort key; TrackML uses at most 18, 14 and about 3,200): checked on the
+ * device, GTF_TRUTH_ERR_RANGE. Node, hit and particle ids are arbitrary int64 (0, negative and
+ * 60-bit ids included). Each of n_rows, n_truth and n_particles is at most 2^30. */
+typedef struct gtf_truth_in {
+    uint32_t struct_size;        /* sizeof(gtf_truth_in) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    int32_t n_rows;              /* rows of the mapping */
+    int32_t n_truth;             /* rows of the truth columns; 0 = the mapping's own hit_id / particle_id */
+    int32_t n_particles;         /* rows of the particles table */
+    int32_t num_layers;          /* distinct (volume, layer) a reference track needs (:66: 4) */
+    int32_t min_volume;          /* the region: min_volume <= volume_id <= max_volume */
+    int32_t max_volume;
+    double pt_cut;               /* sqrt(px*px + py*py) >= pt_cut in fp64 (:46: 1.0) */
+    const int64_t* node_idx;     /* [n_rows] the six columns of the mapping */
+    const int64_t* hit_id;
+    const int64_t* particle_id;
+    const int64_t* volume_id;
+    const int64_t* layer_id;
+    const int64_t* module_id;
+    const int64_t* truth_hit;    /* [n_truth] or NULL with n_truth == 0 */
+    const int64_t* truth_part;
+    const int64_t* part_id;      /* [n_particles] */
+    const double* px;            /* [n_particles] */
+    const double* py;
+} gtf_truth_in;
+
+/* The caller's output arrays at their bound: T, P and R are each at most n_rows. */
+typedef struct gtf_truth_buf {
+    int64_t* node_id;            /* [n_rows] */
+    int32_t* node_ptr;           /* [n_rows + 1] */
+    int64_t* node_part;          /* [n_rows] */
+    int64_t* part_id;            /* [n_rows] */
+    int32_t* part_hits;          /* [n_rows] */
+    uint8_t* part_ref;           /* [n_rows] */
+} gtf_truth_buf;
+
+#define GTF_TRUTH_ERR_MISSING 1u   /* a mapped hit has no truth row (the host's ValueError) */
+#define GTF_TRUTH_ERR_RANGE   2u   /* a volume_id, layer_id or module_id outside [0, 2^21) */
+
+typedef struct gtf_truth_counts {
+    int32_t n_nodes;             /* T */
+    int32_t n_entries;           /* P */
+    int32_t n_particles;         /* R */
+    int32_t n_reference;         /* the sum of part_ref */
+    uint32_t error;              /* GTF_TRUTH_ERR_* */
+    int32_t pad_;
+} gtf_truth_counts;
+
+/* Scratch of gtf_truth_build: positive for zero sizes, non-decreasing in each argument (negative
+ * counts as 0; n_truth == 0 counts as n_rows). About 130 bytes per row at n_truth == n_rows. */
+size_t gtf_truth_build_workspace_bytes(int32_t n_rows, int32_t n_truth, int32_t n_particles);
+
+/* metrics.truth_tables line by line:
+ *   - a particle is high-pT when sqrt(px*px + py*py) >= pt_cut, in fp64 with NumPy's roundings;
+ *   - a mapping row is in the region when its volume lies in the window and its hit_id has at
+ *     least one truth row whose particle is high-pT (np.isin over hits: a row can be selected
+ *     through another row of its hit; with separate truth columns the mapping's own
+ *     particle_id plays no part in the selection);
+ *   - part_id: the distinct particle_id of the region rows, ascending as signed int64;
+ *     part_hits their region rows (repeated rows count); part_ref = 1 with at least num_layers
+ *     distinct (volume, layer) and no (volume, layer, module) twice among the particle's rows;
+ *   - node_id / node_ptr / node_part: the first row of every distinct (node_idx, hit_id) pair,
+ *     grouped by ascending node, a node's entries in mapping-row order; each entry the particle
+ *     of the FIRST truth row, in row order, with that hit id.
+ * Six hipCUB radix sorts (particles, truth rows by hit, rows by packed module key and by
+ * particle, rows by node and by hit), exclusive sums of packed marks, binary searches; no atomic
+ * but the error word's on a violation. Nothing is allocated. Synchronises `stream` once, to fill
+ * *counts; *out then holds buf's pointers and the counts, ready for gtf_score_candidates.
+ * Nothing is written past node_id[T], node_ptr[T + 1], node_part[P], part_*[R].
+ * Returns -2 with GTF_TRUTH_ERR_MISSING or GTF_TRUTH_ERR_RANGE in counts->error (the arrays are
+ * then unspecified); -3 for another ABI of *in; -2 for a null argument or array that is needed,
+ * negative sizes, more than 2^30 rows, min_volume > max_volume or a small workspace, all
+ * decided on the host before any launch. n_rows == 0: returns 0 with zero counts and
+ * node_ptr[0] = 0 (one stream-ordered fill), nothing else written, no workspace needed. */
+int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth* out,
+                    gtf_truth_counts* counts, void* workspace, size_t workspace_bytes,
+                    gtf_stream_t stream);
 
 /* ---- Parabolic-model KL training data -------------------------
  * learn_KL_parabolic_model/src/generate_training_data: the per-edge parabolic
