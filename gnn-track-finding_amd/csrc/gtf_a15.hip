@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 #include "gtf_math.h"
 
 using namespace gtf;

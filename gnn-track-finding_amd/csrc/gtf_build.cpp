@@ -29,10 +29,7 @@
 #include <vector>
 
 #include "../../include/gtf.h"
-
-namespace gtf {
-void set_error(const char* msg);
-}
+#include "gtf_host.h"
 
 namespace {
 

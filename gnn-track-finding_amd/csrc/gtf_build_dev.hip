@@ -32,17 +32,16 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 #include "gtf_pyset.h"
-
-namespace gtf {
-void set_error(const char* msg);
-}
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline int grid(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;
 
 constexpr uint64_t NONE = ~uint64_t(0);
 constexpr int32_t ERR_DUP = 1, ERR_RANGE = 2, ERR_ASYM = 4, ERR_OVER = 8;
@@ -283,69 +282,56 @@ struct BuildWs {
     uint8_t* seen;
     int64_t *words, *toff, *tbl;
     int32_t* scal;   // [0] error bits, [1] changed, [2] valid edges
-    void* cub;
-    size_t cub_bytes, tbl_words;
+    gtf::Scratch cub;
+    size_t tbl_words, total;
 };
-
-size_t cub_need(int64_t n) {
-    size_t a = 0, b = 0, c = 0, d = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
-                                             (int32_t*)nullptr, (int)n);
-    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)n);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (int32_t*)nullptr, (int32_t*)nullptr, (int)n + 1);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, d, (int64_t*)nullptr, (int64_t*)nullptr, (int)n + 1);
-    size_t m = a > b ? a : b;
-    m = m > c ? m : c;
-    return m > d ? m : d;
-}
 
 // capacity bound: a set of k distinct keys has a table of <= 8 max(k, 1) entries, so the
 // component tables (3 per component) take <= 24 N words and the key-order tables (2 per
 // node) <= 16 (S + N)
-BuildWs carve(void* base, int64_t N, int64_t R, bool with_ptrs) {
-    const int64_t E2 = 2 * R, M = N > E2 ? N : E2, n1 = N + 1;
-    char* p = (char*)base;
+BuildWs carve(void* base, int64_t N, int64_t R) {
+    const int64_t E2 = 2 * R, M = N > E2 ? N : E2;
+    const size_t n = (size_t)N, n1 = n + 1, m = (size_t)M, e2 = (size_t)(E2 > 0 ? E2 : 1);
+    gtf::Arena a(base);
     BuildWs w;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
-    w.ids = (uint64_t*)take(8 * N);
-    w.ka = (uint64_t*)take(8 * M);
-    w.kb = (uint64_t*)take(8 * M);
-    w.idx = (int32_t*)take(4 * N);
-    w.iota = (int32_t*)take(4 * M);
-    w.va = (int32_t*)take(4 * M);
-    w.vb = (int32_t*)take(4 * M);
-    w.gk = (uint64_t*)take(8 * (E2 > 0 ? E2 : 1));
-    w.gv = (int32_t*)take(4 * (E2 > 0 ? E2 : 1));
-    w.gdeg = (int32_t*)take(4 * n1);
-    w.gptr = (int32_t*)take(4 * n1);
-    w.lab = (int32_t*)take(4 * n1);
-    w.isroot = (int32_t*)take(4 * n1);
-    w.rank = (int32_t*)take(4 * n1);
-    w.comp = (int32_t*)take(4 * n1);
-    w.size = (int32_t*)take(4 * n1);
-    w.coff = (int32_t*)take(4 * n1);
-    w.memb = (int32_t*)take(4 * n1);
-    w.pos = (int32_t*)take(4 * n1);
-    w.queue = (int32_t*)take(4 * n1);
-    w.rdeg = (int32_t*)take(4 * n1);
-    w.od = (int32_t*)take(4 * n1);
-    w.seen = (uint8_t*)take(n1);
-    w.words = (int64_t*)take(8 * n1);
-    w.toff = (int64_t*)take(8 * n1);
-    w.scal = (int32_t*)take(64);
-    w.cub_bytes = cub_need(M > n1 ? M : n1);
-    w.cub = take(w.cub_bytes);
+    w.ids = a.take<uint64_t>(n);
+    w.ka = a.take<uint64_t>(m);
+    w.kb = a.take<uint64_t>(m);
+    w.idx = a.take<int32_t>(n);
+    w.iota = a.take<int32_t>(m);
+    w.va = a.take<int32_t>(m);
+    w.vb = a.take<int32_t>(m);
+    w.gk = a.take<uint64_t>(e2);
+    w.gv = a.take<int32_t>(e2);
+    w.gdeg = a.take<int32_t>(n1);
+    w.gptr = a.take<int32_t>(n1);
+    w.lab = a.take<int32_t>(n1);
+    w.isroot = a.take<int32_t>(n1);
+    w.rank = a.take<int32_t>(n1);
+    w.comp = a.take<int32_t>(n1);
+    w.size = a.take<int32_t>(n1);
+    w.coff = a.take<int32_t>(n1);
+    w.memb = a.take<int32_t>(n1);
+    w.pos = a.take<int32_t>(n1);
+    w.queue = a.take<int32_t>(n1);
+    w.rdeg = a.take<int32_t>(n1);
+    w.od = a.take<int32_t>(n1);
+    w.seen = a.take<uint8_t>(n1);
+    w.words = a.take<int64_t>(n1);
+    w.toff = a.take<int64_t>(n1);
+    w.scal = a.take<int32_t>(16);
+    const int c = (int)(m > n1 ? m : n1);
+    gtf::CubNeed need;
+    need.sort_pairs<uint64_t, int32_t>(c).sort_keys<uint64_t>(c).scan<int32_t>(c + 1).scan<int64_t>(c + 1);
+    w.cub = need.take(a);
     const int64_t t1 = 24 * (N > 0 ? N : 1), t2 = 16 * (E2 + N + 1);
     w.tbl_words = (size_t)(t1 > t2 ? t1 : t2);
-    w.tbl = (int64_t*)take(8 * w.tbl_words);
-    (void)with_ptrs;
+    w.tbl = a.take<int64_t>(w.tbl_words);
+    w.total = a.used() + 256;
     return w;
 }
 
-size_t carve_bytes(int64_t N, int64_t R) {
-    BuildWs w = carve((void*)(uintptr_t)0, N, R, false);
-    return (size_t)((char*)w.tbl - (char*)0) + al(8 * w.tbl_words) + 256;
-}
+size_t carve_bytes(int64_t N, int64_t R) { return carve(nullptr, N, R).total; }
 
 }  // namespace
 
@@ -358,147 +344,126 @@ size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows) {
 int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
     if (!ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
         (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
-        (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot)) || !workspace) {
-        gtf::set_error("gtf_build_event_csr_device: bad arguments");
-        return -2;
-    }
+        (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot)) || !workspace)
+        return bad("gtf_build_event_csr_device: bad arguments");
+    const char* who = "gtf_build_event_csr_device";
     const int64_t N = ev->n_nodes, R = ev->n_rows, E2 = 2 * R;
-    if (N > INT32_MAX / 2 || E2 > INT32_MAX / 2) {
-        gtf::set_error("gtf_build_event_csr_device: graph too large for int32 indices");
-        return -2;
-    }
-    if (workspace_bytes < carve_bytes(N, R)) {
-        gtf::set_error("gtf_build_event_csr_device: workspace smaller than gtf_build_event_device_workspace_bytes");
-        return -2;
-    }
+    if (N > INT32_MAX / 2 || E2 > INT32_MAX / 2)
+        return bad("gtf_build_event_csr_device: graph too large for int32 indices");
+    if (workspace_bytes < carve_bytes(N, R))
+        return bad("gtf_build_event_csr_device: workspace smaller than gtf_build_event_device_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    BuildWs w = carve(workspace, N, R, true);
-    auto fail = [&](const char* what) {
+    const BuildWs w = carve(workspace, N, R);
+    const gtf::Cub cub{w.cub, st};
+    // a failure that is not a HIP call's: -1 with its own text
+    auto broken = [](const char* what) {
         gtf::set_error(what);
         return -1;
     };
-#define GTF_CK(x, what) \
-    if ((x) != hipSuccess) return fail(what)
+    hipError_t e;
     const int32_t zero4[3] = {0, 0, 0};
-    GTF_CK(hipMemcpyAsync(w.scal, zero4, sizeof(zero4), hipMemcpyHostToDevice, st), "scalars");
+    if ((e = hipMemcpyAsync(w.scal, zero4, sizeof(zero4), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(who, "scalars", e);
     if (N == 0) {
-        GTF_CK(hipMemsetAsync(ev->slot_ptr, 0, 4, st), "memset");
-        GTF_CK(hipMemsetAsync(ev->out_ptr, 0, 4, st), "memset");
-        GTF_CK(hipStreamSynchronize(st), "sync");
+        if ((e = hipMemsetAsync(ev->slot_ptr, 0, 4, st)) != hipSuccess) return fail(who, "memset", e);
+        if ((e = hipMemsetAsync(ev->out_ptr, 0, 4, st)) != hipSuccess) return fail(who, "memset", e);
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
         ev->n_edges = 0;
         ev->n_subgraphs = 0;
         return 0;
     }
     const int64_t M2 = N > E2 ? N : E2;
-    size_t cb;
     // 1. ids -> CSV index
     hipLaunchKernelGGL(k_iota, dim3(grid(M2)), dim3(BLOCK), 0, st, w.iota, M2);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, (const uint64_t*)ev->node_id, w.ids, w.iota, w.idx, (int)N, 0,
-                                              64, st), "sort ids");
+    if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.ids, w.iota, w.idx, (int)N)) != hipSuccess)
+        return fail(who, "sort ids", e);
     hipLaunchKernelGGL(k_check_ids, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.scal);
     // 2. G's successor lists in insertion order
     int32_t m = 0;
     if (R > 0) {
         hipLaunchKernelGGL(k_rows, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx, (int32_t)N,
                            w.ka, w.va);
-        cb = w.cub_bytes;
-        GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kb, w.va, w.vb, (int)E2, 0, 64, st), "sort pairs");
+        if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.vb, (int)E2)) != hipSuccess) return fail(who, "sort pairs", e);
         hipLaunchKernelGGL(k_first, dim3(grid(E2)), dim3(BLOCK), 0, st, w.kb, w.vb, E2, w.ka, w.va);
-        cb = w.cub_bytes;
-        GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.gk, w.va, w.gv, (int)E2, 0, 64, st), "sort succ");
+        if ((e = cub.sort_pairs(w.ka, w.gk, w.va, w.gv, (int)E2)) != hipSuccess) return fail(who, "sort succ", e);
         hipLaunchKernelGGL(k_count_valid, dim3(grid(E2)), dim3(BLOCK), 0, st, w.gk, E2, w.scal + 2);
     }
     int32_t scal[3];
-    GTF_CK(hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-    if (scal[0] & ERR_RANGE) { gtf::set_error("gtf_build_event_csr_device: node ids must be in [0, 2^61 - 1)"); return -2; }
-    if (scal[0] & ERR_DUP) { gtf::set_error("gtf_build_event_csr_device: duplicate node id"); return -2; }
+    if ((e = hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return fail(who, "read", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
+    if (scal[0] & ERR_RANGE) return bad("gtf_build_event_csr_device: node ids must be in [0, 2^61 - 1)");
+    if (scal[0] & ERR_DUP) return bad("gtf_build_event_csr_device: duplicate node id");
     m = scal[2];
     const uint64_t* gkey = w.gk;   // kept edges by (u, insertion time); value: v
     const int32_t* gdst = w.gv;
-    GTF_CK(hipMemsetAsync(w.gdeg, 0, 4 * (N + 1), st), "memset");
+    if ((e = hipMemsetAsync(w.gdeg, 0, 4 * (N + 1), st)) != hipSuccess) return fail(who, "memset", e);
     if (m > 0) hipLaunchKernelGGL(k_gdeg, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, m, w.gdeg);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.gdeg, w.gptr, (int)N + 1, st), "scan");
+    if ((e = cub.scan(w.gdeg, w.gptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     // 3. weakly connected components, labelled by their minimum CSV index
     hipLaunchKernelGGL(k_lab_init, dim3(grid(N)), dim3(BLOCK), 0, st, w.lab, N);
     for (int round = 0; m > 0; round++) {
-        if (round > 200) return fail("gtf_build_event_csr_device: components did not converge");
+        if (round > 200) return broken("gtf_build_event_csr_device: components did not converge");
         int32_t z = 0, changed = 0;
-        GTF_CK(hipMemcpyAsync(w.scal + 1, &z, 4, hipMemcpyHostToDevice, st), "flag");
+        if ((e = hipMemcpyAsync(w.scal + 1, &z, 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(who, "flag", e);
         hipLaunchKernelGGL(k_hook, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, m, w.lab, w.scal + 1);
         hipLaunchKernelGGL(k_compress, dim3(grid(N)), dim3(BLOCK), 0, st, w.lab, N);
-        GTF_CK(hipMemcpyAsync(&changed, w.scal + 1, 4, hipMemcpyDeviceToHost, st), "flag");
-        GTF_CK(hipStreamSynchronize(st), "sync");
+        if ((e = hipMemcpyAsync(&changed, w.scal + 1, 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return fail(who, "flag", e);
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
         if (!changed) break;
     }
     hipLaunchKernelGGL(k_isroot, dim3(grid(N + 1)), dim3(BLOCK), 0, st, w.lab, N, w.isroot);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.isroot, w.rank, (int)N + 1, st), "scan");
+    if ((e = cub.scan(w.isroot, w.rank, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     int32_t n_sub = 0;
-    GTF_CK(hipMemcpyAsync(&n_sub, w.rank + N, 4, hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipMemsetAsync(w.size, 0, 4 * (N + 1), st), "memset");
+    if ((e = hipMemcpyAsync(&n_sub, w.rank + N, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
+    if ((e = hipMemsetAsync(w.size, 0, 4 * (N + 1), st)) != hipSuccess) return fail(who, "memset", e);
     hipLaunchKernelGGL(k_comp_of, dim3(grid(N)), dim3(BLOCK), 0, st, w.lab, w.rank, N, w.comp, w.size, w.ka);
-    GTF_CK(hipStreamSynchronize(st), "sync");
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.size, w.coff, n_sub + 1, st), "scan");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
+    if ((e = cub.scan(w.size, w.coff, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     // 4. node order of every component's copy: CSV-index order (the stable sort by
     // component), replaced by the set order for components under half the graph
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kb, w.iota, w.memb, (int)N, 0, 32, st),
-           "sort members");
+    if ((e = cub.sort_pairs(w.ka, w.kb, w.iota, w.memb, (int)N, 32)) != hipSuccess) return fail(who, "sort members", e);
     hipLaunchKernelGGL(k_order_sorted, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, w.comp, w.size, N, ev->order);
     hipLaunchKernelGGL(k_comp_words, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, n_sub, N, w.words);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.words, w.toff, n_sub + 1, st), "scan");
+    if ((e = cub.scan(w.words, w.toff, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     int64_t words = 0;
-    GTF_CK(hipMemcpyAsync(&words, w.toff + n_sub, 8, hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-    if ((size_t)words > w.tbl_words) return fail("gtf_build_event_csr_device: set tables exceed the workspace bound");
-    GTF_CK(hipMemsetAsync(w.seen, 0, N, st), "memset");
+    if ((e = hipMemcpyAsync(&words, w.toff + n_sub, 8, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return fail(who, "read", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
+    if ((size_t)words > w.tbl_words) return broken("gtf_build_event_csr_device: set tables exceed the workspace bound");
+    if ((e = hipMemsetAsync(w.seen, 0, N, st)) != hipSuccess) return fail(who, "memset", e);
     hipLaunchKernelGGL(k_comp_order, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub, N, w.gptr,
                        gkey, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen, ev->order, w.scal);
     hipLaunchKernelGGL(k_pos, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, w.comp, N, w.pos, ev->sub_id);
     // 5. slots: (packed receiver, packed sender) in order; the out-lists; the key orders
-    GTF_CK(hipMemsetAsync(w.rdeg, 0, 4 * (N + 1), st), "memset");
+    if ((e = hipMemsetAsync(w.rdeg, 0, 4 * (N + 1), st)) != hipSuccess) return fail(who, "memset", e);
     if (m > 0) {
         hipLaunchKernelGGL(k_slot_keys, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, m, w.pos, w.ka, w.rdeg);
-        cb = w.cub_bytes;
-        GTF_CK(hipcub::DeviceRadixSort::SortKeys(w.cub, cb, w.ka, w.kb, m, 0, 64, st), "sort slots");
+        if ((e = cub.sort_keys(w.ka, w.kb, m)) != hipSuccess) return fail(who, "sort slots", e);
         hipLaunchKernelGGL(k_slot_src, dim3(grid(m)), dim3(BLOCK), 0, st, w.kb, m, ev->slot_src);
     }
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.rdeg, ev->slot_ptr, (int)N + 1, st), "scan");
+    if ((e = cub.scan(w.rdeg, ev->slot_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     hipLaunchKernelGGL(k_outdeg, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->order, w.gdeg, N, w.od);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.od, ev->out_ptr, (int)N + 1, st), "scan");
+    if ((e = cub.scan(w.od, ev->out_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     if (m > 0)
         hipLaunchKernelGGL(k_out_slot, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, w.gptr, m, w.pos, ev->slot_ptr,
                            ev->slot_src, ev->out_ptr, ev->out_slot);
     hipLaunchKernelGGL(k_tse_words, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->slot_ptr, N, w.words);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.words, w.toff, (int)N + 1, st), "scan");
-    GTF_CK(hipMemcpyAsync(&words, w.toff + N, 8, hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-    if ((size_t)words > w.tbl_words) return fail("gtf_build_event_csr_device: set tables exceed the workspace bound");
+    if ((e = cub.scan(w.words, w.toff, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
+    if ((e = hipMemcpyAsync(&words, w.toff + N, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
+    if ((size_t)words > w.tbl_words) return broken("gtf_build_event_csr_device: set tables exceed the workspace bound");
     hipLaunchKernelGGL(k_tse_rank, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, ev->slot_ptr, ev->slot_src, w.gptr,
                        gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank, w.scal);
-    GTF_CK(hipGetLastError(), "launch");
-    GTF_CK(hipMemcpyAsync(scal, w.scal, 4, hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-    if (scal[0] & ERR_OVER) {
-        gtf::set_error("gtf_build_event_csr_device: a set held more keys than its table was sized for");
-        return -1;
-    }
-    if (scal[0] & ERR_ASYM) {
-        gtf::set_error("gtf_build_event_csr_device: neighbour without an in-edge (graph not symmetric)");
-        return -1;
-    }
+    if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
+    if ((e = hipMemcpyAsync(scal, w.scal, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
+    if (scal[0] & ERR_OVER) return broken("gtf_build_event_csr_device: a set held more keys than its table was sized for");
+    if (scal[0] & ERR_ASYM) return broken("gtf_build_event_csr_device: neighbour without an in-edge (graph not symmetric)");
     ev->n_edges = m;
     ev->n_subgraphs = n_sub;
     return 0;
-#undef GTF_CK
 }
 
 }  // extern "C"

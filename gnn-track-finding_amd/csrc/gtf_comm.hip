@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 

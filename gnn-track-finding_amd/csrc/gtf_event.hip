@@ -19,11 +19,14 @@
 #include <stdio.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using gtf::bad;
+using gtf::fail;
+
+constexpr int BLOCK = gtf::BLOCK256;
 constexpr int MAXC = GTF_FILL_MAX_COLUMNS;
 constexpr int MAX_BLOCKS = 2048;   // of one loop's grid (8 a CU); longer arrays stride
 
@@ -105,18 +108,6 @@ __global__ __launch_bounds__(BLOCK) void k_fill(ColTab tab) {
     if (c.lg == 3) fill_words<uint64_t>(c);
     else if (c.lg == 2) fill_words<uint32_t>(c);
     else fill_words<uint8_t>(c);
-}
-
-int bad(const char* what) {
-    gtf::set_error(what);
-    return -2;
-}
-
-int fail(const char* who, const char* what, hipError_t e) {
-    char m[200];
-    snprintf(m, sizeof(m), "%s: %s: %s", who, what, hipGetErrorString(e));
-    gtf::set_error(m);
-    return -1;
 }
 
 }  // namespace

@@ -29,17 +29,16 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 #include "gtf_pyset.h"
-
-namespace gtf {
-void set_error(const char* msg);
-}
 
 namespace {
 
-constexpr int BLOCK = 256;
-inline int grid(int n) { return (n + BLOCK - 1) / BLOCK; }
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;
 
 // ------------------------------------------------------------------ CCA
 __global__ void __launch_bounds__(BLOCK) k_ex_init(int n, int n_sub, int32_t* label, uint8_t* inactive,
@@ -494,62 +493,61 @@ __global__ void __launch_bounds__(BLOCK) k_ex_flags(int n, gtf_extract_io io) {
 // component ends labelled by its minimum node index. 0, or -1 with the error set.
 template <bool ANY>
 int cca_rounds(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id, int n_sub, int32_t* label,
-               uint8_t* inactive, int32_t* flag, hipStream_t st, const char* fail, const char* stuck) {
+               uint8_t* inactive, int32_t* flag, hipStream_t st, const char* who) {
     const int n = g->n_nodes;
     const int nb = grid(n > n_sub ? n : n_sub);
     hipLaunchKernelGGL(k_ex_init, dim3(nb), dim3(BLOCK), 0, st, n, n_sub, label, inactive, flag);
     if (g->n_slots > 0)
         hipLaunchKernelGGL(k_ex_inactive, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, sub_id, inactive);
     int32_t changed = 0;
+    hipError_t err;
     for (int round = 0; round < 64; round++) {
         int32_t zero = 0;
-        if (hipMemcpyAsync(flag, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        if ((err = hipMemcpyAsync(flag, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(who, "CCA round", err);
         if (g->n_slots > 0)
             hipLaunchKernelGGL(k_ex_hook<ANY>, dim3(grid(g->n_slots)), dim3(BLOCK), 0, st, *g, *e, label, flag);
         hipLaunchKernelGGL(k_ex_compress, dim3(grid(n)), dim3(BLOCK), 0, st, n, label);
-        if (hipMemcpyAsync(&changed, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            gtf::set_error(fail);
-            return -1;
-        }
+        if ((err = hipMemcpyAsync(&changed, flag, sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (err = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(who, "CCA round", err);
         if (!changed) break;
     }
-    if (changed) { gtf::set_error(stuck); return -1; }
+    if (changed) {
+        char m[120];
+        snprintf(m, sizeof(m), "%s: CCA did not converge", who);
+        gtf::set_error(m);
+        return -1;
+    }
     return 0;
 }
+
+// the hipcub calls of the extraction: one sort of (key, member) pairs, one scan of the starts
+gtf::CubNeed ex_cub_need(int n) { return gtf::CubNeed().sort_pairs<uint64_t, int32_t>(n).scan<int32_t>(n); }
 
 struct ExWs {
     uint64_t *keys_in, *keys_out;
     int32_t *vals_in, *vals_out, *is_start, *cidx, *cand_ptr, *flag;
     uint8_t* inactive;
-    void* cub;
-    size_t cub_bytes;
+    gtf::Scratch cub;
+    size_t total;
 };
 
-size_t al(size_t x) { return (x + 255) & ~size_t(255); }
-
-size_t cub_bytes(int n) {
-    size_t a = 0, b = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                             (int32_t*)nullptr, (int32_t*)nullptr, n);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, n);
-    return a > b ? a : b;
-}
-
-ExWs carve_ex(void* base, int n, int n_sub) {
-    char* p = (char*)base;
+// n >= 1
+ExWs carve_ex(const void* base, int n, int n_sub) {
+    gtf::Arena a(base);
     ExWs w;
-    w.keys_in = (uint64_t*)p; p += al(8 * (size_t)n);
-    w.keys_out = (uint64_t*)p; p += al(8 * (size_t)n);
-    w.vals_in = (int32_t*)p; p += al(4 * (size_t)n);
-    w.vals_out = (int32_t*)p; p += al(4 * (size_t)n);
-    w.is_start = (int32_t*)p; p += al(4 * (size_t)n);
-    w.cidx = (int32_t*)p; p += al(4 * (size_t)n);
-    w.cand_ptr = (int32_t*)p; p += al(4 * ((size_t)n + 1));
-    w.flag = (int32_t*)p; p += 256;
-    w.inactive = (uint8_t*)p; p += al((size_t)(n_sub > 0 ? n_sub : 1));
-    w.cub_bytes = cub_bytes(n);
-    w.cub = p;
+    w.keys_in = a.take<uint64_t>(n);
+    w.keys_out = a.take<uint64_t>(n);
+    w.vals_in = a.take<int32_t>(n);
+    w.vals_out = a.take<int32_t>(n);
+    w.is_start = a.take<int32_t>(n);
+    w.cidx = a.take<int32_t>(n);
+    w.cand_ptr = a.take<int32_t>((size_t)n + 1);
+    w.flag = a.take<int32_t>(1);
+    w.inactive = a.take<uint8_t>(n_sub > 0 ? n_sub : 1);
+    w.cub = ex_cub_need(n).take(a);
+    w.total = a.used() + 256;
     return w;
 }
 
@@ -687,50 +685,38 @@ struct OrdWs {
     int32_t *vals_in, *memb, *idx, *is_start, *cidx, *cptr, *label, *queue, *so_flag, *so_size, *scal;
     int64_t *words, *toff, *tbl;
     uint8_t *seen, *inactive;
-    void* cub;
-    size_t cub_bytes, tbl_words, total;
+    gtf::Scratch cub;
+    size_t tbl_words, total;
 };
-
-size_t ord_cub_bytes(int n) {
-    size_t a = cub_bytes(n), b = 0, c = 0, d = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, n + 1);
-    (void)hipcub::DeviceReduce::Sum(nullptr, c, (int32_t*)nullptr, (int32_t*)nullptr, n);
-    (void)hipcub::DeviceReduce::Max(nullptr, d, (int32_t*)nullptr, (int32_t*)nullptr, n);
-    a = a > b ? a : b;
-    a = a > c ? a : c;
-    return a > d ? a : d;
-}
 
 // n >= 1. The set tables: a set of k distinct keys has a table of <= 8 max(k, 1) entries and a
 // component takes three, so <= 24 N words (the bound argued in gtf_build_dev.hip's carve)
 OrdWs carve_ord(void* base, int n, int n_sub) {
-    char* p = (char*)base;
+    gtf::Arena a(base);
     OrdWs w;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
     const size_t n1 = (size_t)n + 1;
-    w.keys_in = (uint64_t*)take(8 * (size_t)n);
-    w.keys_out = (uint64_t*)take(8 * (size_t)n);
-    w.ids = (uint64_t*)take(8 * (size_t)n);
-    w.words = (int64_t*)take(8 * n1);
-    w.toff = (int64_t*)take(8 * n1);
-    w.vals_in = (int32_t*)take(4 * (size_t)n);
-    w.memb = (int32_t*)take(4 * (size_t)n);
-    w.idx = (int32_t*)take(4 * (size_t)n);
-    w.is_start = (int32_t*)take(4 * (size_t)n);
-    w.cidx = (int32_t*)take(4 * (size_t)n);
-    w.cptr = (int32_t*)take(4 * n1);
-    w.label = (int32_t*)take(4 * (size_t)n);
-    w.queue = (int32_t*)take(4 * (size_t)n);
-    w.so_flag = (int32_t*)take(4 * (size_t)n);
-    w.so_size = (int32_t*)take(4 * (size_t)n);
-    w.scal = (int32_t*)take(64);
-    w.seen = (uint8_t*)take((size_t)n);
-    w.inactive = (uint8_t*)take((size_t)(n_sub > 0 ? n_sub : 1));
-    w.cub_bytes = ord_cub_bytes(n);
-    w.cub = take(w.cub_bytes);
+    w.keys_in = a.take<uint64_t>(n);
+    w.keys_out = a.take<uint64_t>(n);
+    w.ids = a.take<uint64_t>(n);
+    w.words = a.take<int64_t>(n1);
+    w.toff = a.take<int64_t>(n1);
+    w.vals_in = a.take<int32_t>(n);
+    w.memb = a.take<int32_t>(n);
+    w.idx = a.take<int32_t>(n);
+    w.is_start = a.take<int32_t>(n);
+    w.cidx = a.take<int32_t>(n);
+    w.cptr = a.take<int32_t>(n1);
+    w.label = a.take<int32_t>(n);
+    w.queue = a.take<int32_t>(n);
+    w.so_flag = a.take<int32_t>(n);
+    w.so_size = a.take<int32_t>(n);
+    w.scal = a.take<int32_t>(16);
+    w.seen = a.take<uint8_t>(n);
+    w.inactive = a.take<uint8_t>(n_sub > 0 ? n_sub : 1);
+    w.cub = ex_cub_need(n).scan<int64_t>(n + 1).sum<int32_t>(n).max<int32_t>(n).take(a);
     w.tbl_words = 24 * (size_t)n;
-    w.tbl = (int64_t*)take(8 * w.tbl_words);
-    w.total = (size_t)(p - (char*)base) + 256;
+    w.tbl = a.take<int64_t>(w.tbl_words);
+    w.total = a.used() + 256;
     return w;
 }
 
@@ -825,33 +811,24 @@ __global__ void k_out_counts(int n, int n_sub, gtf_extract_out o, const int64_t*
 struct OutWs {
     int32_t *notext, *pre, *scal;
     int64_t *in64, *ext, *rem, *frag, *frag_in;
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
 };
 
-size_t out_cub_bytes(int m) {
-    size_t a = 0, b = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (int32_t*)nullptr, (int32_t*)nullptr, m + 1);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, m + 1);
-    return a > b ? a : b;
-}
-
 OutWs carve_out(void* base, int n, int n_sub) {
-    char* p = (char*)base;
+    gtf::Arena a(base);
     OutWs w;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
     const size_t n1 = (size_t)n + 1, s1 = (size_t)n_sub + 1, m1 = n1 > s1 ? n1 : s1;
-    w.in64 = (int64_t*)take(8 * m1);
-    w.frag_in = (int64_t*)take(8 * s1);
-    w.ext = (int64_t*)take(8 * n1);
-    w.rem = (int64_t*)take(8 * s1);
-    w.frag = (int64_t*)take(8 * s1);
-    w.notext = (int32_t*)take(4 * n1);
-    w.pre = (int32_t*)take(4 * n1);
-    w.scal = (int32_t*)take(64);
-    w.cub_bytes = out_cub_bytes((int)(m1 - 1));
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base) + 256;
+    w.in64 = a.take<int64_t>(m1);
+    w.frag_in = a.take<int64_t>(s1);
+    w.ext = a.take<int64_t>(n1);
+    w.rem = a.take<int64_t>(s1);
+    w.frag = a.take<int64_t>(s1);
+    w.notext = a.take<int32_t>(n1);
+    w.pre = a.take<int32_t>(n1);
+    w.scal = a.take<int32_t>(16);
+    w.cub = gtf::CubNeed().scan<int32_t>((int)m1).scan<int64_t>((int)m1).take(a);
+    w.total = a.used() + 256;
     return w;
 }
 
@@ -861,26 +838,25 @@ extern "C" {
 
 int gtf_subgraph_ptr_device(const int32_t* sub_id, int32_t n_nodes, int32_t n_sub, int32_t* sub_ptr,
                             gtf_stream_t stream) {
-    if (!sub_ptr || n_nodes < 0 || n_sub < 0 || (n_nodes && !sub_id) || (n_nodes > 0 && n_sub == 0)) {
-        gtf::set_error("gtf_subgraph_ptr_device: bad arguments");
-        return -2;
-    }
+    const char* who = "gtf_subgraph_ptr_device";
+    if (!sub_ptr || n_nodes < 0 || n_sub < 0 || (n_nodes && !sub_id) || (n_nodes > 0 && n_sub == 0))
+        return bad("gtf_subgraph_ptr_device: bad arguments");
     hipStream_t st = (hipStream_t)stream;
+    hipError_t err;
     if (n_nodes == 0) {
-        if (hipMemsetAsync(sub_ptr, 0, 4 * ((size_t)n_sub + 1), st) != hipSuccess) { gtf::set_error("gtf_subgraph_ptr_device: memset"); return -1; }
+        if ((err = hipMemsetAsync(sub_ptr, 0, 4 * ((size_t)n_sub + 1), st)) != hipSuccess) return fail(who, "memset", err);
         return 0;
     }
     int32_t last = n_nodes;
-    bool ok = hipMemcpyAsync(sub_ptr + n_sub, &last, 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    const hipError_t set = hipMemcpyAsync(sub_ptr + n_sub, &last, 4, hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(k_sub_ptr, dim3(grid(n_nodes)), dim3(BLOCK), 0, st, n_nodes, n_sub, sub_id, sub_ptr,
                        sub_ptr + n_sub);
-    ok = ok && hipMemcpyAsync(&last, sub_ptr + n_sub, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
-         hipStreamSynchronize(st) == hipSuccess;
-    if (!ok) { gtf::set_error("gtf_subgraph_ptr_device: launch failed"); return -1; }
-    if (last != n_nodes) {
-        gtf::set_error("gtf_subgraph_ptr_device: sub_id must number the subgraphs 0 .. n_sub - 1 with the nodes grouped");
-        return -2;
-    }
+    if ((err = set) != hipSuccess ||
+        (err = hipMemcpyAsync(&last, sub_ptr + n_sub, 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (err = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(who, "launch", err);
+    if (last != n_nodes)
+        return bad("gtf_subgraph_ptr_device: sub_id must number the subgraphs 0 .. n_sub - 1 with the nodes grouped");
     return 0;
 }
 
@@ -895,68 +871,52 @@ int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int
                                gtf_order_counts* counts, gtf_stream_t stream) {
     const char* who = "gtf_candidate_order_device";
     if (int rc = gtf::check_abi(g, who)) return rc;
-    if (!e || !counts || !workspace || g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0 || n_sub < 0) {
-        gtf::set_error("gtf_candidate_order_device: null argument or negative size");
-        return -2;
-    }
+    if (!e || !counts || !workspace || g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0 || n_sub < 0)
+        return bad("gtf_candidate_order_device: null argument or negative size");
     *counts = gtf_order_counts{0, 0, 0, 0};
     const int n = g->n_nodes;
     if (n == 0) return 0;
     if (!sub_id || !sub_ptr || !node_id || !order_key || !g->slot_ptr || !g->out_ptr ||
-        (g->n_slots && (!g->slot_src || !g->slot_dst || !g->is_edge || !e->act)) || (g->n_edges && !g->out_slot)) {
-        gtf::set_error("gtf_candidate_order_device: missing array (slot_ptr, slot_src, slot_dst, out_ptr, out_slot, "
-                       "is_edge, act, sub_id, sub_ptr, node_id, order_key)");
-        return -2;
-    }
-    if (workspace_bytes < gtf_candidate_order_workspace_bytes(n, g->n_slots, n_sub)) {
-        gtf::set_error("gtf_candidate_order_device: workspace smaller than gtf_candidate_order_workspace_bytes");
-        return -2;
-    }
+        (g->n_slots && (!g->slot_src || !g->slot_dst || !g->is_edge || !e->act)) || (g->n_edges && !g->out_slot))
+        return bad("gtf_candidate_order_device: missing array (slot_ptr, slot_src, slot_dst, out_ptr, out_slot, "
+                   "is_edge, act, sub_id, sub_ptr, node_id, order_key)");
+    if (workspace_bytes < gtf_candidate_order_workspace_bytes(n, g->n_slots, n_sub))
+        return bad("gtf_candidate_order_device: workspace smaller than gtf_candidate_order_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    OrdWs w = carve_ord(workspace, n, n_sub);
-    auto fail = [&](const char* what) { gtf::set_error(what); return -1; };
-#define GTF_CK(x, what) \
-    if ((x) != hipSuccess) return fail("gtf_candidate_order_device: " what)
-    GTF_CK(hipMemsetAsync(w.scal, 0, 64, st), "memset");
-    if (int rc = cca_rounds<true>(g, e, sub_id, n_sub, w.label, w.inactive, w.scal + 8, st,
-                                  "gtf_candidate_order_device: CCA round failed",
-                                  "gtf_candidate_order_device: CCA did not converge"))
-        return rc;
+    const OrdWs w = carve_ord(workspace, n, n_sub);
+    const gtf::Cub cub{w.cub, st};
+    hipError_t err;
+    if ((err = hipMemsetAsync(w.scal, 0, 64, st)) != hipSuccess) return fail(who, "memset", err);
+    if (int rc = cca_rounds<true>(g, e, sub_id, n_sub, w.label, w.inactive, w.scal + 8, st, who)) return rc;
     // members of every component in node order, the component pointers and their count
     hipLaunchKernelGGL(k_ord_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.label, w.keys_in, w.vals_in, w.seen);
-    size_t cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys_out, w.vals_in, w.memb, n, 0, 64, st),
-           "sort members");
+    if ((err = cub.sort_pairs(w.keys_in, w.keys_out, w.vals_in, w.memb, n)) != hipSuccess)
+        return fail(who, "sort members", err);
     hipLaunchKernelGGL(k_ex_starts, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.keys_out, w.is_start);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.is_start, w.cidx, n, st), "scan");
+    if ((err = cub.scan(w.is_start, w.cidx, n)) != hipSuccess) return fail(who, "scan", err);
     hipLaunchKernelGGL(k_ex_ptr, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.is_start, w.cidx, w.cptr, w.scal + OS_NCOMP);
     hipLaunchKernelGGL(k_ord_rank, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.memb, w.is_start, w.cidx, w.cptr, sub_id,
                        sub_ptr, w.inactive, order_key);
     // node id -> index (keys_in is free again; vals_in still holds 0 .. n - 1)
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, (const uint64_t*)node_id, w.ids, w.vals_in, w.idx, n, 0, 64,
-                                              st), "sort ids");
+    if ((err = cub.sort_pairs((const uint64_t*)node_id, w.ids, w.vals_in, w.idx, n)) != hipSuccess)
+        return fail(who, "sort ids", err);
     hipLaunchKernelGGL(k_ord_check_ids, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.ids, w.scal + OS_ERR);
     // the set-ordered components: table offsets and counts by scans, then one thread each
     hipLaunchKernelGGL(k_ord_words, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, w.scal + OS_NCOMP, w.cptr, w.memb,
                        sub_id, sub_ptr, w.inactive, w.words, w.so_flag, w.so_size);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.words, w.toff, n + 1, st), "scan");
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceReduce::Sum(w.cub, cb, w.so_flag, w.scal + OS_NSET, n, st), "sum");
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceReduce::Max(w.cub, cb, w.so_size, w.scal + OS_MAXSET, n, st), "max");
+    if ((err = cub.scan(w.words, w.toff, n + 1)) != hipSuccess) return fail(who, "scan", err);
+    if ((err = cub.sum(w.so_flag, w.scal + OS_NSET, n)) != hipSuccess) return fail(who, "sum", err);
+    if ((err = cub.max(w.so_size, w.scal + OS_MAXSET, n)) != hipSuccess) return fail(who, "max", err);
     hipLaunchKernelGGL(k_ord_walk, dim3(grid(n)), dim3(BLOCK), 0, st, *g, e->act, n, w.scal + OS_NCOMP, w.cptr, w.memb,
                        w.so_flag, node_id, w.ids, w.idx, w.toff, w.tbl, (int64_t)w.tbl_words, w.queue, w.seen,
                        order_key, w.scal + OS_ERR);
-    GTF_CK(hipGetLastError(), "launch");
+    if ((err = hipGetLastError()) != hipSuccess) return fail(who, "launch", err);
     int32_t scal[4];
-    GTF_CK(hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-#undef GTF_CK
-    if (scal[OS_ERR] & OERR_RANGE) { gtf::set_error("gtf_candidate_order_device: node ids must be in [0, 2^61 - 1)"); return -2; }
-    if (scal[OS_ERR] & OERR_DUP) { gtf::set_error("gtf_candidate_order_device: duplicate node id"); return -2; }
+    if ((err = hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return fail(who, "read", err);
+    if ((err = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", err);
+    if (scal[OS_ERR] & OERR_RANGE) return bad("gtf_candidate_order_device: node ids must be in [0, 2^61 - 1)");
+    if (scal[OS_ERR] & OERR_DUP) return bad("gtf_candidate_order_device: duplicate node id");
     if (scal[OS_ERR] & OERR_OVER) {
         gtf::set_error("gtf_candidate_order_device: a set held more keys than its table was sized for");
         return -1;
@@ -972,104 +932,79 @@ size_t gtf_extract_outputs_workspace_bytes(int32_t n_nodes, int32_t n_sub) {
 int gtf_extract_outputs(const gtf_graph* g, const gtf_extract_io* io, int32_t fragment,
                         const void* extract_workspace, const gtf_extract_out* out, void* workspace,
                         size_t workspace_bytes, gtf_extract_out_counts* counts, gtf_stream_t stream) {
-    if (int rc = gtf::check_abi(g, "gtf_extract_outputs")) return rc;
-    if (!io || !out || !counts || !workspace || !extract_workspace || g->n_nodes < 0 || fragment < 1) {
-        gtf::set_error("gtf_extract_outputs: null argument, negative size or fragment < 1");
-        return -2;
-    }
+    const char* who = "gtf_extract_outputs";
+    if (int rc = gtf::check_abi(g, who)) return rc;
+    if (!io || !out || !counts || !workspace || !extract_workspace || g->n_nodes < 0 || fragment < 1)
+        return bad("gtf_extract_outputs: null argument, negative size or fragment < 1");
     *counts = gtf_extract_out_counts{0, 0, 0, 0, 0, 0};
     const int n = g->n_nodes, n_sub = io->n_sub;
     if (n == 0) return 0;
     if (!io->sub_id || !io->sub_ptr || !io->label || !io->status || !io->pval_xy || !io->pval_zr || !io->extracted ||
         !io->n_candidates || n_sub <= 0 || !out->left || !out->keep ||
-        ((out->cand_ids || out->rem_ids || out->frag_ids) && !out->node_id)) {
-        gtf::set_error("gtf_extract_outputs: missing arrays (the results of gtf_extract_candidates, left, keep, "
-                       "node_id for the id lists)");
-        return -2;
-    }
-    if (workspace_bytes < gtf_extract_outputs_workspace_bytes(n, n_sub)) {
-        gtf::set_error("gtf_extract_outputs: workspace smaller than gtf_extract_outputs_workspace_bytes");
-        return -2;
-    }
+        ((out->cand_ids || out->rem_ids || out->frag_ids) && !out->node_id))
+        return bad("gtf_extract_outputs: missing arrays (the results of gtf_extract_candidates, left, keep, "
+                   "node_id for the id lists)");
+    if (workspace_bytes < gtf_extract_outputs_workspace_bytes(n, n_sub))
+        return bad("gtf_extract_outputs: workspace smaller than gtf_extract_outputs_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    const ExWs x = carve_ex(const_cast<void*>(extract_workspace), n, n_sub);
-    OutWs w = carve_out(workspace, n, n_sub);
-    auto fail = [&](const char* what) { gtf::set_error(what); return -1; };
-#define GTF_CK(x, what) \
-    if ((x) != hipSuccess) return fail("gtf_extract_outputs: " what)
+    const ExWs x = carve_ex(extract_workspace, n, n_sub);
+    const OutWs w = carve_out(workspace, n, n_sub);
+    const gtf::Cub cub{w.cub, st};
+    hipError_t err;
     // nodes that stay, counted before every node: left[s] is a difference at sub_ptr
     hipLaunchKernelGGL(k_out_notext, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, io->extracted, w.notext);
-    size_t cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.notext, w.pre, n + 1, st), "scan");
+    if ((err = cub.scan(w.notext, w.pre, n + 1)) != hipSuccess) return fail(who, "scan", err);
     hipLaunchKernelGGL(k_out_sub, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, n_sub, fragment, io->sub_ptr, w.pre,
                        out->left, w.in64, w.frag_in);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in64, w.rem, n_sub + 1, st), "scan");
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.frag_in, w.frag, n_sub + 1, st), "scan");
+    if ((err = cub.scan(w.in64, w.rem, n_sub + 1)) != hipSuccess) return fail(who, "scan", err);
+    if ((err = cub.scan(w.frag_in, w.frag, n_sub + 1)) != hipSuccess) return fail(who, "scan", err);
     hipLaunchKernelGGL(k_out_nodes, dim3(grid(n)), dim3(BLOCK), 0, st, n, n_sub, fragment, *io, *out, w.pre, w.rem,
                        w.frag);
     // the extracted candidates, in the order the extraction's sort left them
     hipLaunchKernelGGL(k_out_cand, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, io->n_candidates, x.cand_ptr, x.vals_out,
                        io->label, io->status, w.in64);
-    cb = w.cub_bytes;
-    GTF_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in64, w.ext, n + 1, st), "scan");
+    if ((err = cub.scan(w.in64, w.ext, n + 1)) != hipSuccess) return fail(who, "scan", err);
     hipLaunchKernelGGL(k_out_members, dim3(grid(n)), dim3(BLOCK), 0, st, n, *io, *out, x.vals_out, x.is_start, x.cidx,
                        x.cand_ptr, w.ext);
     hipLaunchKernelGGL(k_out_counts, dim3(1), dim3(64), 0, st, n, n_sub, *out, w.ext, w.rem, w.frag, w.scal);
-    GTF_CK(hipGetLastError(), "launch");
+    if ((err = hipGetLastError()) != hipSuccess) return fail(who, "launch", err);
     int32_t c[6];
-    GTF_CK(hipMemcpyAsync(c, w.scal, sizeof(c), hipMemcpyDeviceToHost, st), "read");
-    GTF_CK(hipStreamSynchronize(st), "sync");
-#undef GTF_CK
+    if ((err = hipMemcpyAsync(c, w.scal, sizeof(c), hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", err);
+    if ((err = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", err);
     *counts = gtf_extract_out_counts{c[0], c[1], c[2], c[3], c[4], c[5]};
     return 0;
 }
 
 size_t gtf_extract_workspace_bytes(int32_t n_nodes, int32_t n_sub) {
-    const int n = n_nodes > 0 ? n_nodes : 1;
-    return 6 * al(8 * (size_t)n) + al(4 * ((size_t)n + 1)) + 256 + al((size_t)(n_sub > 0 ? n_sub : 1)) +
-           cub_bytes(n) + 256;
+    return carve_ex(nullptr, n_nodes > 0 ? n_nodes : 1, n_sub).total;
 }
 
 int gtf_extract_candidates(const gtf_graph* g, const gtf_edges* e, const gtf_extract_io* io,
                            const gtf_extract_params* p, void* workspace, gtf_stream_t stream) {
-    if (int rc = gtf::check_abi(g, "gtf_extract_candidates")) return rc;
-    if (!e || !io || !p || !workspace) { gtf::set_error("gtf_extract_candidates: null argument"); return -2; }
+    const char* who = "gtf_extract_candidates";
+    if (int rc = gtf::check_abi(g, who)) return rc;
+    if (!e || !io || !p || !workspace) return bad("gtf_extract_candidates: null argument");
     const int n = g->n_nodes;
     if (n <= 0) return 0;
     if (!io->xyzr || !io->vivl || !io->sub_id || !io->sub_ptr || !io->gnn || !io->label || !io->status ||
-        !io->pval_xy || !io->pval_zr || !io->extracted || !io->n_candidates || p->fragment < 3) {
-        gtf::set_error("gtf_extract_candidates: missing arrays or fragment < 3");
-        return -2;
-    }
+        !io->pval_xy || !io->pval_zr || !io->extracted || !io->n_candidates || p->fragment < 3)
+        return bad("gtf_extract_candidates: missing arrays or fragment < 3");
     hipStream_t st = (hipStream_t)stream;
-    ExWs w = carve_ex(workspace, n, io->n_sub);
-    if (int rc = cca_rounds<false>(g, e, io->sub_id, io->n_sub, io->label, w.inactive, w.flag, st,
-                                   "gtf_extract_candidates: CCA round failed",
-                                   "gtf_extract_candidates: CCA did not converge"))
-        return rc;
+    const ExWs w = carve_ex(workspace, n, io->n_sub);
+    const gtf::Cub cub{w.cub, st};
+    hipError_t err;
+    if (int rc = cca_rounds<false>(g, e, io->sub_id, io->n_sub, io->label, w.inactive, w.flag, st, who)) return rc;
     hipLaunchKernelGGL(k_ex_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, io->sub_id, io->sub_ptr, w.inactive,
                        io->order_key, io->label, w.keys_in, w.vals_in);
-    size_t cb = w.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.keys_in, w.keys_out, w.vals_in, w.vals_out, n, 0, 64, st) !=
-        hipSuccess) {
-        gtf::set_error("gtf_extract_candidates: sort failed");
-        return -1;
-    }
+    if ((err = cub.sort_pairs(w.keys_in, w.keys_out, w.vals_in, w.vals_out, n)) != hipSuccess) return fail(who, "sort", err);
     hipLaunchKernelGGL(k_ex_starts, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.keys_out, w.is_start);
-    cb = w.cub_bytes;
-    if (hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.is_start, w.cidx, n, st) != hipSuccess) {
-        gtf::set_error("gtf_extract_candidates: scan failed");
-        return -1;
-    }
+    if ((err = cub.scan(w.is_start, w.cidx, n)) != hipSuccess) return fail(who, "scan", err);
     hipLaunchKernelGGL(k_ex_ptr, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.is_start, w.cidx, w.cand_ptr,
                        io->n_candidates);
     hipLaunchKernelGGL(k_ex_candidate, dim3(grid(n)), dim3(BLOCK), 0, st, *io, *p, w.vals_out, w.cand_ptr,
                        io->n_candidates);
     hipLaunchKernelGGL(k_ex_flags, dim3(grid(n)), dim3(BLOCK), 0, st, n, *io);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { gtf::set_error(hipGetErrorString(err)); return -1; }
+    if ((err = hipGetLastError()) != hipSuccess) return fail(who, "launch", err);
     return 0;
 }
 

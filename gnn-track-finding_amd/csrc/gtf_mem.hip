@@ -10,67 +10,57 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 
-namespace gtf {
-void set_error(const char* msg);
-}
-
-namespace {
-int fail(const char* what, hipError_t e) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
-    gtf::set_error(msg);
-    return -1;
-}
-}  // namespace
+using gtf::fail;
 
 extern "C" {
 
 int gtf_device_init(int32_t device) {
     const hipError_t e = hipSetDevice(device);
-    return e == hipSuccess ? 0 : fail("gtf_device_init", e);
+    return e == hipSuccess ? 0 : fail("gtf_device_init", "hipSetDevice", e);
 }
 
 int gtf_malloc(void** ptr, size_t bytes) {
-    if (!ptr) return fail("gtf_malloc", hipErrorInvalidValue);
+    if (!ptr) return fail("gtf_malloc", "null ptr", hipErrorInvalidValue);
     *ptr = nullptr;
     const hipError_t e = hipMalloc(ptr, bytes ? bytes : 256);   // never a null device pointer
-    return e == hipSuccess ? 0 : fail("gtf_malloc", e);
+    return e == hipSuccess ? 0 : fail("gtf_malloc", "hipMalloc", e);
 }
 
 int gtf_free(void* ptr) {
     const hipError_t e = hipFree(ptr);
-    return e == hipSuccess ? 0 : fail("gtf_free", e);
+    return e == hipSuccess ? 0 : fail("gtf_free", "hipFree", e);
 }
 
 int gtf_memcpy_htod(void* dst, const void* src, size_t bytes, gtf_stream_t stream) {
     if (!bytes) return 0;
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("gtf_memcpy_htod", e);
+    return e == hipSuccess ? 0 : fail("gtf_memcpy_htod", "copy", e);
 }
 
 int gtf_memcpy_dtoh(void* dst, const void* src, size_t bytes, gtf_stream_t stream) {
     if (!bytes) return 0;
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("gtf_memcpy_dtoh", e);
+    return e == hipSuccess ? 0 : fail("gtf_memcpy_dtoh", "copy", e);
 }
 
 int gtf_memcpy_dtod(void* dst, const void* src, size_t bytes, gtf_stream_t stream) {
     if (!bytes) return 0;
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("gtf_memcpy_dtod", e);
+    return e == hipSuccess ? 0 : fail("gtf_memcpy_dtod", "copy", e);
 }
 
 int gtf_memset(void* dst, int32_t value, size_t bytes, gtf_stream_t stream) {
     if (!bytes) return 0;
     const hipError_t e = hipMemsetAsync(dst, value, bytes, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("gtf_memset", e);
+    return e == hipSuccess ? 0 : fail("gtf_memset", "memset", e);
 }
 
 int gtf_stream_synchronize(gtf_stream_t stream) {
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("gtf_stream_synchronize", e);
+    return e == hipSuccess ? 0 : fail("gtf_stream_synchronize", "synchronize", e);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 #include "gtf_math.h"
 
 using namespace gtf;
@@ -1018,11 +1019,6 @@ constexpr int NBLOCK = GTF_NODE_BLOCK;
 
 thread_local char g_err[512] = "";
 
-int fail(const char* what, hipError_t e) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return -1;
-}
-
 int check_graph(const gtf_graph* g) {
     if (int rc = check_abi(g, "gtf_pass")) return rc;
     if (g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0) {
@@ -1098,7 +1094,7 @@ int launch_extrap_edges(const gtf_graph* g, gtf_nodes* n, gtf_states* uts, gtf_e
                            w, slot_lo, slot_hi, slots);
     if (events) (void)hipEventRecord((hipEvent_t)events[2], st);
     hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : fail("extrapolate launch", err);
+    return err == hipSuccess ? 0 : fail("gtf_pass", "extrapolate launch", err);
 }
 
 
@@ -1180,7 +1176,7 @@ int launch_ops(const gtf_graph* g, gtf_nodes* n, gtf_states* tse, gtf_states* ut
         launch_serial_rest(g, n, T, U, e, p, w, ops, chi2, kl, st);
     }
     hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : fail("node kernel launch", err);
+    return err == hipSuccess ? 0 : fail("gtf_pass", "node kernel launch", err);
 }
 
 // compile-time op sequence (the stage entry points)
@@ -1252,7 +1248,7 @@ int launch_seq(const gtf_graph* g, gtf_nodes* n, gtf_states* tse, gtf_states* ut
         launch_serial_rest(g, n, T, U, e, p, w, ops, chi2, kl, st);
     }
     hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : fail("node kernel launch", err);
+    return err == hipSuccess ? 0 : fail("gtf_pass", "node kernel launch", err);
 }
 
 
@@ -1322,7 +1318,7 @@ size_t gtf_workspace_bytes(int32_t n_nodes, int32_t n_slots) {
 int gtf_workspace_init(void* ws, gtf_stream_t stream) {
     // error word + gtf_diag (no diagnostics)
     hipError_t e = hipMemsetAsync(ws, 0, WS_HEAD, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("workspace init", e);
+    return e == hipSuccess ? 0 : fail("gtf_workspace_init", "memset", e);
 }
 
 int gtf_uts_materialize(const gtf_graph* g, gtf_states* uts, gtf_stream_t stream) {
@@ -1336,12 +1332,12 @@ int gtf_uts_materialize(const gtf_graph* g, gtf_states* uts, gtf_stream_t stream
     if (g->n_slots > 0)
         hipLaunchKernelGGL(k_uts_materialize, dim3(grid(g->n_slots)), dim3(BLOCK), 0, (hipStream_t)stream, *g, *uts);
     hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : fail("materialize launch", err);
+    return err == hipSuccess ? 0 : fail("gtf_uts_materialize", "launch", err);
 }
 
 int gtf_clear_errors(void* ws, gtf_stream_t stream) {
     hipError_t e = hipMemsetAsync(ws, 0, GTF_DIAG_OFFSET, (hipStream_t)stream);   // (keeps gtf_diag)
-    return e == hipSuccess ? 0 : fail("clear errors", e);
+    return e == hipSuccess ? 0 : fail("gtf_clear_errors", "memset", e);
 }
 
 int gtf_set_diagnostics(void* ws, const gtf_diag* d, gtf_stream_t stream) {
@@ -1350,13 +1346,13 @@ int gtf_set_diagnostics(void* ws, const gtf_diag* d, gtf_stream_t stream) {
     hipError_t e = hipMemcpyAsync((char*)ws + GTF_DIAG_OFFSET, d ? d : &z, sizeof(gtf_diag), hipMemcpyHostToDevice,
                                   (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);   // (d / z are host stack memory)
-    return e == hipSuccess ? 0 : fail("set diagnostics", e);
+    return e == hipSuccess ? 0 : fail("gtf_set_diagnostics", "copy", e);
 }
 
 int gtf_read_errors(void* ws, uint32_t* flags, gtf_stream_t stream) {
     hipError_t e = hipMemcpyAsync(flags, ws, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return e == hipSuccess ? 0 : fail("read errors", e);
+    return e == hipSuccess ? 0 : fail("gtf_read_errors", "copy", e);
 }
 
 int gtf_message_passing(const gtf_graph* g, gtf_nodes* n, gtf_states* uts, gtf_edges* e, const gtf_params* p,

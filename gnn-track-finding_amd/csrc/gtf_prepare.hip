@@ -33,15 +33,17 @@
 #include <stdio.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 
-constexpr int BLOCK = 256;          // 4 wavefronts
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;   // 4 wavefronts
 constexpr int WAVES = BLOCK / 64;
 constexpr int NCLS = 9, SCLS = 3, CLS = NCLS + SCLS;   // node classes, then sender classes
-inline int grid(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Prep {
     int32_t N, S, E;
@@ -296,27 +298,24 @@ __global__ __launch_bounds__(BLOCK) void k_lanes(Prep a, int n_o4, int n_o8) {
 
 struct PrepWs {
     int32_t *hist, *scan, *scal, *sched, *seg, *slot_dst;
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
     int32_t nb;
 };
 
 PrepWs carve(void* base, int64_t N, int64_t S) {
     PrepWs w;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
+    gtf::Arena a(base);
     w.nb = (int32_t)((N + BLOCK - 1) / BLOCK);
     const size_t m = (size_t)CLS * (size_t)w.nb + 1;
-    w.hist = (int32_t*)take(4 * m);
-    w.scan = (int32_t*)take(4 * m);
-    w.scal = (int32_t*)take(64);
-    w.sched = (int32_t*)take(4 * (size_t)N);        // used when the caller asks for no sched / sched_seg /
-    w.seg = (int32_t*)take(8 * (size_t)N);          // slot_dst: the slot and out-edge kernels read them
-    w.slot_dst = (int32_t*)take(4 * (size_t)S);
-    w.cub_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.cub_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int)m);
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base);
+    w.hist = a.take<int32_t>(m);
+    w.scan = a.take<int32_t>(m);
+    w.scal = a.take<int32_t>(16);
+    w.sched = a.take<int32_t>((size_t)N);       // used when the caller asks for no sched / sched_seg /
+    w.seg = a.take<int32_t>(2 * (size_t)N);     // slot_dst: the slot and out-edge kernels read them
+    w.slot_dst = a.take<int32_t>((size_t)S);
+    w.cub = gtf::CubNeed().scan<int32_t>((int)m).take(a);
+    w.total = a.used();
     return w;
 }
 
@@ -332,16 +331,13 @@ extern "C" {
 
 size_t gtf_graph_prepare_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_edges) {
     (void)n_edges;   // (no per-edge scratch; kept in the signature for later layouts)
-    return carve((void*)(uintptr_t)0, n_nodes > 0 ? n_nodes : 0, n_slots > 0 ? n_slots : 0).total;
+    return carve(nullptr, n_nodes > 0 ? n_nodes : 0, n_slots > 0 ? n_slots : 0).total;
 }
 
 int gtf_graph_prepare(gtf_graph* g, const gtf_graph_tables* t, void* workspace, size_t workspace_bytes,
                       gtf_stream_t stream) {
-    if (int rc = gtf::check_abi(g, "gtf_graph_prepare")) return rc;
-    auto bad = [](const char* what) {
-        gtf::set_error(what);
-        return -2;
-    };
+    const char* who = "gtf_graph_prepare";
+    if (int rc = gtf::check_abi(g, who)) return rc;
     if (g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0) return bad("gtf_graph_prepare: negative sizes");
     const int32_t N = g->n_nodes, S = g->n_slots, E = g->n_edges;
     if (!t) return bad("gtf_graph_prepare: null gtf_graph_tables");
@@ -383,20 +379,15 @@ int gtf_graph_prepare(gtf_graph* g, const gtf_graph_tables* t, void* workspace, 
     int32_t c[CLS] = {0};
     if (!empty) {
         hipStream_t st = (hipStream_t)stream;
-        auto fail = [&](const char* what, hipError_t e) {
-            char m[200];
-            snprintf(m, sizeof(m), "gtf_graph_prepare: %s: %s", what, hipGetErrorString(e));
-            gtf::set_error(m);
-            return -1;
-        };
+        const gtf::Cub cub{w.cub, st};
+        hipError_t e;
         // 1. the schedules, and their class sizes to the host
         hipLaunchKernelGGL(k_hist, dim3(a.nb), dim3(BLOCK), 0, st, a);
-        size_t cb = w.cub_bytes;
-        hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, a.hist, a.scan, CLS * a.nb + 1, st);
-        if (e != hipSuccess) return fail("scan", e);
+        if ((e = cub.scan(a.hist, a.scan, CLS * a.nb + 1)) != hipSuccess) return fail(who, "scan", e);
         hipLaunchKernelGGL(k_scatter, dim3(a.nb), dim3(BLOCK), 0, st, a);
-        if ((e = hipMemcpyAsync(c, a.scal, sizeof(c), hipMemcpyDeviceToHost, st)) != hipSuccess) return fail("counts", e);
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail("synchronize", e);
+        if ((e = hipMemcpyAsync(c, a.scal, sizeof(c), hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return fail(who, "counts", e);
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "synchronize", e);
         int64_t nodes = 0;
         for (int q = 0; q < CLS; q++) {
             if (c[q] < 0 || c[q] > N) return bad("gtf_graph_prepare: inconsistent slot_ptr / out_ptr");
@@ -421,7 +412,7 @@ int gtf_graph_prepare(gtf_graph* g, const gtf_graph_tables* t, void* workspace, 
         const int64_t lanes = 4 * (int64_t)c[NCLS] + 8 * (int64_t)c[NCLS + 1];
         if (a.out_lanes && lanes > 0)
             hipLaunchKernelGGL(k_lanes, dim3(grid(lanes)), dim3(BLOCK), 0, st, a, c[NCLS], c[NCLS + 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return fail("launch", e);
+        if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
     }
 
     // the written tables and the counts into *g; a table not asked for leaves its optional field NULL

@@ -32,41 +32,41 @@
 #include <stdio.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;
 constexpr int G = 16;                  // lanes of a small candidate's group
 constexpr int PER_WAVE = 64 / G;       // candidates of a wavefront
 constexpr int PER_BLOCK = PER_WAVE * (BLOCK / 64);
 constexpr uint64_t NONE = ~uint64_t(0);
 constexpr int32_t MAX_MEMBERS = 1 << 30;
-inline int grid(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Ws {
     int32_t *c_row, *c_good, *c_total;   // [n_cand] the passing candidate's particle row (-1: none), its counts
     int32_t* mrow;                       // [M + 1] start of the member's node_part row
     int64_t *mlen, *off;                 // [M + 1] its length; the exclusive sum
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
 };
 
 Ws carve(void* base, int64_t C, int64_t M) {
     Ws w;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
-    w.c_row = (int32_t*)take(4 * (size_t)C);
-    w.c_good = (int32_t*)take(4 * (size_t)C);
-    w.c_total = (int32_t*)take(4 * (size_t)C);
-    w.mrow = (int32_t*)take(4 * (size_t)(M + 1));
-    w.mlen = (int64_t*)take(8 * (size_t)(M + 1));
-    w.off = (int64_t*)take(8 * (size_t)(M + 1));
-    w.cub_bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, w.cub_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (int)(M + 1));
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base);
+    gtf::Arena a(base);
+    const size_t c = (size_t)C, m1 = (size_t)M + 1;
+    w.c_row = a.take<int32_t>(c);
+    w.c_good = a.take<int32_t>(c);
+    w.c_total = a.take<int32_t>(c);
+    w.mrow = a.take<int32_t>(m1);
+    w.mlen = a.take<int64_t>(m1);
+    w.off = a.take<int64_t>(m1);
+    w.cub = gtf::CubNeed().scan<int64_t>((int)m1).take(a);
+    w.total = a.used();
     return w;
 }
 
@@ -74,23 +74,19 @@ struct FinWs {
     uint64_t* keys;          // [R] sorted
     int32_t *vin, *vout;     // [R] particle rows
     int32_t* scal;           // [2] n_reconstructed, error
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
 };
 
 FinWs carve_fin(void* base, int64_t R) {
     FinWs w;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
-    w.scal = (int32_t*)take(64);
-    w.keys = (uint64_t*)take(8 * (size_t)R);
-    w.vin = (int32_t*)take(4 * (size_t)R);
-    w.vout = (int32_t*)take(4 * (size_t)R);
-    w.cub_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, w.cub_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                             (int32_t*)nullptr, (int32_t*)nullptr, (int)R, 0, 64);
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base);
+    gtf::Arena a(base);
+    w.scal = a.take<int32_t>(16);
+    w.keys = a.take<uint64_t>((size_t)R);
+    w.vin = a.take<int32_t>((size_t)R);
+    w.vout = a.take<int32_t>((size_t)R);
+    w.cub = gtf::CubNeed().sort_pairs<uint64_t, int32_t>((int)R).take(a);
+    w.total = a.used();
     return w;
 }
 
@@ -323,31 +319,10 @@ __global__ __launch_bounds__(BLOCK) void k_records(Fin a) {
     if (a.out_hits) a.out_hits[i] = a.part_hits[r];
 }
 
-int bad(const char* what) {
-    gtf::set_error(what);
-    return -2;
-}
-
-int fail(const char* who, const char* what, hipError_t e) {
-    char m[200];
-    snprintf(m, sizeof(m), "%s: %s: %s", who, what, hipGetErrorString(e));
-    gtf::set_error(m);
-    return -1;
-}
-
 // the gtf_truth of another layout of include/gtf.h: -3; a null or inconsistent one: -2
 int check_truth(const gtf_truth* t, const char* who) {
     char m[220];
-    if (!t) {
-        snprintf(m, sizeof(m), "%s: null gtf_truth", who);
-        return bad(m);
-    }
-    if (t->struct_size != (uint32_t)sizeof(gtf_truth) || t->abi_version != GTF_ABI_VERSION) {
-        snprintf(m, sizeof(m), "%s: gtf_truth ABI mismatch (caller struct_size %u, abi_version %u; library %u, %u)", who,
-                 t->struct_size, t->abi_version, (unsigned)sizeof(gtf_truth), (unsigned)GTF_ABI_VERSION);
-        gtf::set_error(m);
-        return -3;
-    }
+    if (int rc = gtf::check_abi(t, who, "gtf_truth", "gtf_truth")) return rc;
     if (t->n_nodes < 0 || t->n_entries < 0 || t->n_particles < 0) {
         snprintf(m, sizeof(m), "%s: negative sizes in gtf_truth", who);
         return bad(m);
@@ -396,11 +371,11 @@ int gtf_score_reset(const gtf_score_state* state, gtf_stream_t stream) {
 }
 
 size_t gtf_score_workspace_bytes(int32_t n_cand, int32_t n_members) {
-    return carve((void*)(uintptr_t)0, n_cand > 0 ? n_cand : 0, n_members > 0 ? n_members : 0).total;
+    return carve(nullptr, n_cand > 0 ? n_cand : 0, n_members > 0 ? n_members : 0).total;
 }
 
 size_t gtf_score_finish_workspace_bytes(int32_t n_particles) {
-    return carve_fin((void*)(uintptr_t)0, n_particles > 0 ? n_particles : 0).total;
+    return carve_fin(nullptr, n_particles > 0 ? n_particles : 0).total;
 }
 
 int gtf_score_candidates(const gtf_truth* truth, const int32_t* cand_ptr, const int64_t* cand_ids,
@@ -440,9 +415,7 @@ int gtf_score_candidates(const gtf_truth* truth, const int32_t* cand_ptr, const 
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     hipLaunchKernelGGL(k_members, dim3(grid((int64_t)a.M + 1)), dim3(BLOCK), 0, st, a);
-    size_t cb = a.w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(a.w.cub, cb, a.w.mlen, a.w.off, a.M + 1, st)) != hipSuccess)
-        return fail(who, "scan", e);
+    if ((e = gtf::Cub{a.w.cub, st}.scan(a.w.mlen, a.w.off, a.M + 1)) != hipSuccess) return fail(who, "scan", e);
     hipLaunchKernelGGL(k_vote, dim3((n_cand + PER_BLOCK - 1) / PER_BLOCK), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_winners, dim3(grid(n_cand)), dim3(BLOCK), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
@@ -475,9 +448,7 @@ int gtf_score_finish(const gtf_truth* truth, const gtf_score_state* state, uint6
     hipError_t e;
     if (R > 0) {
         hipLaunchKernelGGL(k_iota, dim3(grid(R)), dim3(BLOCK), 0, st, a);
-        size_t cb = a.w.cub_bytes;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(a.w.cub, cb, a.best_key, a.w.keys, a.w.vin, a.w.vout, R, 0, 64,
-                                                    st)) != hipSuccess)
+        if ((e = gtf::Cub{a.w.cub, st}.sort_pairs(a.best_key, a.w.keys, a.w.vin, a.w.vout, R)) != hipSuccess)
             return fail(who, "sort", e);
     }
     hipLaunchKernelGGL(k_records, dim3(grid(R > 0 ? R : 1)), dim3(BLOCK), 0, st, a);

@@ -14,11 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
-
-namespace gtf {
-void set_error(const char* msg);
-}
+#include "gtf_host.h"
 
 namespace {
 

@@ -36,17 +36,19 @@
 #include <type_traits>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;
 constexpr int MAXC = 32;              // columns per gather launch
 constexpr int GATHER_BLOCKS = 4096;   // blocks of a gather launch, over its columns (16 a CU)
 constexpr uint32_t MAGIC = 0x67735562u;
 constexpr int64_t DROPPED = -2, INSIDE = -1;   // slot codes; >= 0: an orphan's order key
-inline int grid(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 // the plan's header, at offset 0 of the workspace
 struct Hdr {
@@ -64,38 +66,34 @@ struct Ws {
     int64_t* code;
     // n_sub-dependent part, after everything apply and gather read
     int32_t *sub_cnt, *sub_flag, *sub_new;
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
 };
 
-Ws carve(void* base, int64_t N, int64_t S, int64_t nsub) {
+Ws carve(const void* base, int64_t N, int64_t S, int64_t nsub) {
     Ws w;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
-    w.hdr = (Hdr*)take(sizeof(Hdr));
-    w.scal = (int32_t*)take(64);
-    w.flag = (int32_t*)take(4 * (size_t)(N + 1));
-    w.new_idx = (int32_t*)take(4 * (size_t)(N + 1));
-    w.scnt = (int32_t*)take(4 * (size_t)(N + 1));
-    w.sptr = (int32_t*)take(4 * (size_t)(N + 1));
-    w.ocnt = (int32_t*)take(4 * (size_t)(N + 1));
-    w.optr = (int32_t*)take(4 * (size_t)(N + 1));
-    w.node_sub = (int32_t*)take(4 * (size_t)N);
-    w.node_map = (int32_t*)take(4 * (size_t)N);
-    w.node_solo = (uint8_t*)take((size_t)N);
-    w.slot_dst = (int32_t*)take(4 * (size_t)S);
-    w.slot_new = (int32_t*)take(4 * (size_t)S);
-    w.slot_map = (int32_t*)take(4 * (size_t)S);
-    w.code = (int64_t*)take(8 * (size_t)S);
-    w.sub_cnt = (int32_t*)take(4 * (size_t)(nsub + 1));
-    w.sub_flag = (int32_t*)take(4 * (size_t)(nsub + 1));
-    w.sub_new = (int32_t*)take(4 * (size_t)(nsub + 1));
-    size_t a = 0, b = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (int32_t*)nullptr, (int32_t*)nullptr, (int)(N + 1));
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int)(nsub + 1));
-    w.cub_bytes = a > b ? a : b;
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base);
+    gtf::Arena a(base);
+    const size_t n = (size_t)N, n1 = n + 1, s = (size_t)S, b1 = (size_t)nsub + 1;
+    w.hdr = a.take<Hdr>(1);
+    w.scal = a.take<int32_t>(16);
+    w.flag = a.take<int32_t>(n1);
+    w.new_idx = a.take<int32_t>(n1);
+    w.scnt = a.take<int32_t>(n1);
+    w.sptr = a.take<int32_t>(n1);
+    w.ocnt = a.take<int32_t>(n1);
+    w.optr = a.take<int32_t>(n1);
+    w.node_sub = a.take<int32_t>(n);
+    w.node_map = a.take<int32_t>(n);
+    w.node_solo = a.take<uint8_t>(n);
+    w.slot_dst = a.take<int32_t>(s);
+    w.slot_new = a.take<int32_t>(s);
+    w.slot_map = a.take<int32_t>(s);
+    w.code = a.take<int64_t>(s);
+    w.sub_cnt = a.take<int32_t>(b1);
+    w.sub_flag = a.take<int32_t>(b1);
+    w.sub_new = a.take<int32_t>(b1);
+    w.cub = gtf::CubNeed().scan<int32_t>((int)n1).scan<int32_t>((int)b1).take(a);
+    w.total = a.used();
     return w;
 }
 
@@ -401,25 +399,13 @@ __global__ __launch_bounds__(BLOCK) void k_send_mw(Send a) {
     a.send_mw[k] = mw;
 }
 
-int bad(const char* what) {
-    gtf::set_error(what);
-    return -2;
-}
-
-int fail(const char* who, const char* what, hipError_t e) {
-    char m[200];
-    snprintf(m, sizeof(m), "%s: %s: %s", who, what, hipGetErrorString(e));
-    gtf::set_error(m);
-    return -1;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t gtf_graph_subset_workspace_bytes(int32_t n_nodes, int32_t n_slots, int32_t n_edges, int32_t n_sub) {
     (void)n_edges;   // (no per-edge scratch: the out view is walked per sender)
-    return carve((void*)(uintptr_t)0, n_nodes > 0 ? n_nodes : 0, n_slots > 0 ? n_slots : 0, n_sub > 0 ? n_sub : 0).total;
+    return carve(nullptr, n_nodes > 0 ? n_nodes : 0, n_slots > 0 ? n_slots : 0, n_sub > 0 ? n_sub : 0).total;
 }
 
 int gtf_graph_subset_plan(const gtf_graph* g, const int32_t* tse_rank, const int32_t* uts_rank,
@@ -459,15 +445,11 @@ int gtf_graph_subset_plan(const gtf_graph* g, const int32_t* tse_rank, const int
     if (S > 0) hipLaunchKernelGGL(k_classify, dim3(grid(S)), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_count, dim3(grid(N)), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_subflag, dim3(grid((int64_t)n_sub + 1)), dim3(BLOCK), 0, st, a);
-    size_t cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.flag, w.new_idx, N + 1, st)) != hipSuccess) return fail(who, "scan", e);
-    cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.scnt, w.sptr, N + 1, st)) != hipSuccess) return fail(who, "scan", e);
-    cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.ocnt, w.optr, N + 1, st)) != hipSuccess) return fail(who, "scan", e);
-    cb = w.cub_bytes;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.sub_flag, w.sub_new, n_sub + 1, st)) != hipSuccess)
-        return fail(who, "scan", e);
+    const gtf::Cub cub{w.cub, st};
+    if ((e = cub.scan(w.flag, w.new_idx, N + 1)) != hipSuccess) return fail(who, "scan", e);
+    if ((e = cub.scan(w.scnt, w.sptr, N + 1)) != hipSuccess) return fail(who, "scan", e);
+    if ((e = cub.scan(w.ocnt, w.optr, N + 1)) != hipSuccess) return fail(who, "scan", e);
+    if ((e = cub.scan(w.sub_flag, w.sub_new, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     if (S > 0) hipLaunchKernelGGL(k_pos, dim3(grid(S)), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_finish, dim3(grid(N)), dim3(BLOCK), 0, st, a, (int64_t)((char*)w.node_map - (char*)workspace),
                        (int64_t)((char*)w.slot_map - (char*)workspace));
@@ -498,7 +480,7 @@ int gtf_graph_subset_apply(const gtf_graph* g, const void* workspace, const gtf_
     a.N = N; a.S = S; a.E = E;
     a.slot_src = g->slot_src; a.out_ptr = g->out_ptr; a.out_slot = g->out_slot; a.is_edge = g->is_edge;
     a.o = *out;
-    a.w = carve(const_cast<void*>(workspace), N, S, 0);   // (the n_sub-dependent part is not read here)
+    a.w = carve(workspace, N, S, 0);   // (the n_sub-dependent part is not read here)
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_apply_nodes, dim3(grid(N)), dim3(BLOCK), 0, st, a);
     if (S > 0 && (a.o.slot_map || a.o.slot_src)) hipLaunchKernelGGL(k_apply_slots, dim3(grid(S)), dim3(BLOCK), 0, st, a);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 #include "gtf_math.h"
 
 namespace {

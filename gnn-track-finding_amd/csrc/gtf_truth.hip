@@ -39,18 +39,20 @@
 #include <stdio.h>
 
 #include "../../include/gtf.h"
-#include "gtf_math.h"
+#include "gtf_host.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+using gtf::bad;
+using gtf::fail;
+using gtf::grid;
+
+constexpr int BLOCK = gtf::BLOCK256;
 constexpr int32_t MAX_ROWS = 1 << 30;
 constexpr uint64_t SIGN = uint64_t(1) << 63;
 constexpr int ID_BITS = 21;                       // volume, layer, module: [0, 2^21)
 constexpr int64_t ID_LIMIT = int64_t(1) << ID_BITS;
 enum { S_T = 0, S_P, S_R, S_REF, S_ERR, S_WORDS };
-inline int grid(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Ws {
     int32_t* scal;                    // [S_WORDS]
@@ -64,49 +66,41 @@ struct Ws {
     uint8_t* sel;                     // [N] region row
     int64_t *in_a, *in_b, *sum_a, *sum_b;   // [N + 1] packed marks and their exclusive sums
     int32_t *pos, *ref;               // [N + 1] position of particle r's head; its reference flag
-    void* cub;
-    size_t cub_bytes, total;
+    gtf::Scratch cub;
+    size_t total;
 };
 
 Ws carve(void* base, int64_t N, int64_t NT, int64_t NP) {
     Ws w;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes ? bytes : 1); return (void*)q; };
-    const int64_t M = (N > NT ? (N > NP ? N : NP) : (NT > NP ? NT : NP)) + 1;
-    w.scal = (int32_t*)take(64);
-    w.ka = (uint64_t*)take(8 * (size_t)M);
-    w.kb = (uint64_t*)take(8 * (size_t)M);
-    w.kc = (uint64_t*)take(8 * (size_t)M);
-    w.va = (int32_t*)take(4 * (size_t)M);
-    w.vb = (int32_t*)take(4 * (size_t)M);
-    w.vc = (int32_t*)take(4 * (size_t)M);
-    w.pk = (uint64_t*)take(8 * (size_t)(NP + 1));
-    w.pf = (int32_t*)take(4 * (size_t)(NP + 1));
-    w.ps = (int32_t*)take(4 * (size_t)(NP + 1));
-    w.tk = (uint64_t*)take(8 * (size_t)(NT + 1));
-    w.tidx = (int32_t*)take(4 * (size_t)(NT + 1));
-    w.tflag = (int32_t*)take(4 * (size_t)(NT + 1));
-    w.tfs = (int32_t*)take(4 * (size_t)(NT + 1));
-    w.ts = (int32_t*)take(4 * (size_t)(NT + 1));
-    w.row_part = (int64_t*)take(8 * (size_t)N);
-    w.sel = (uint8_t*)take((size_t)N);
-    w.in_a = (int64_t*)take(8 * (size_t)(N + 1));
-    w.in_b = (int64_t*)take(8 * (size_t)(N + 1));
-    w.sum_a = (int64_t*)take(8 * (size_t)(N + 1));
-    w.sum_b = (int64_t*)take(8 * (size_t)(N + 1));
-    w.pos = (int32_t*)take(4 * (size_t)(N + 1));
-    w.ref = (int32_t*)take(4 * (size_t)(N + 1));
-    size_t a = 0, b = 0, c = 0, d = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
-                                             (int32_t*)nullptr, (int)M, 0, 64);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int)M);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, c, (int32_t*)nullptr, (int32_t*)nullptr, (int)M);
-    (void)hipcub::DeviceReduce::Sum(nullptr, d, (int32_t*)nullptr, (int32_t*)nullptr, (int)M);
-    w.cub_bytes = a > b ? a : b;
-    if (c > w.cub_bytes) w.cub_bytes = c;
-    if (d > w.cub_bytes) w.cub_bytes = d;
-    w.cub = take(w.cub_bytes);
-    w.total = (size_t)(p - (char*)base);
+    gtf::Arena a(base);
+    const size_t m = (size_t)(N > NT ? (N > NP ? N : NP) : (NT > NP ? NT : NP)) + 1;
+    const size_t n = (size_t)N, n1 = n + 1, t1 = (size_t)NT + 1, p1 = (size_t)NP + 1;
+    w.scal = a.take<int32_t>(16);
+    w.ka = a.take<uint64_t>(m);
+    w.kb = a.take<uint64_t>(m);
+    w.kc = a.take<uint64_t>(m);
+    w.va = a.take<int32_t>(m);
+    w.vb = a.take<int32_t>(m);
+    w.vc = a.take<int32_t>(m);
+    w.pk = a.take<uint64_t>(p1);
+    w.pf = a.take<int32_t>(p1);
+    w.ps = a.take<int32_t>(p1);
+    w.tk = a.take<uint64_t>(t1);
+    w.tidx = a.take<int32_t>(t1);
+    w.tflag = a.take<int32_t>(t1);
+    w.tfs = a.take<int32_t>(t1);
+    w.ts = a.take<int32_t>(t1);
+    w.row_part = a.take<int64_t>(n);
+    w.sel = a.take<uint8_t>(n);
+    w.in_a = a.take<int64_t>(n1);
+    w.in_b = a.take<int64_t>(n1);
+    w.sum_a = a.take<int64_t>(n1);
+    w.sum_b = a.take<int64_t>(n1);
+    w.pos = a.take<int32_t>(n1);
+    w.ref = a.take<int32_t>(n1);
+    const int mi = (int)m;
+    w.cub = gtf::CubNeed().sort_pairs<uint64_t, int32_t>(mi).scan<int64_t>(mi).scan<int32_t>(mi).sum<int32_t>(mi).take(a);
+    w.total = a.used();
     return w;
 }
 
@@ -308,38 +302,20 @@ __global__ __launch_bounds__(BLOCK) void k_csr(Build a) {
     }
 }
 
-int bad(const char* what) {
-    gtf::set_error(what);
-    return -2;
-}
-
-int fail(const char* what, hipError_t e) {
-    char m[200];
-    snprintf(m, sizeof(m), "gtf_truth_build: %s: %s", what, hipGetErrorString(e));
-    gtf::set_error(m);
-    return -1;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t gtf_truth_build_workspace_bytes(int32_t n_rows, int32_t n_truth, int32_t n_particles) {
     const int64_t N = n_rows > 0 ? n_rows : 0;
-    return carve((void*)(uintptr_t)0, N, n_truth > 0 ? n_truth : N, n_particles > 0 ? n_particles : 0).total;
+    return carve(nullptr, N, n_truth > 0 ? n_truth : N, n_particles > 0 ? n_particles : 0).total;
 }
 
 int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth* out, gtf_truth_counts* counts,
                     void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
+    const char* who = "gtf_truth_build";
     char m[260];
-    if (!in) return bad("gtf_truth_build: null gtf_truth_in");
-    if (in->struct_size != (uint32_t)sizeof(gtf_truth_in) || in->abi_version != GTF_ABI_VERSION) {
-        snprintf(m, sizeof(m), "gtf_truth_build: gtf_truth_in ABI mismatch (caller struct_size %u, abi_version %u; "
-                 "library %u, %u)", in->struct_size, in->abi_version, (unsigned)sizeof(gtf_truth_in),
-                 (unsigned)GTF_ABI_VERSION);
-        gtf::set_error(m);
-        return -3;
-    }
+    if (int rc = gtf::check_abi(in, who, "gtf_truth_in", "gtf_truth_in")) return rc;
     if (!buf || !out || !counts) return bad("gtf_truth_build: null buf, out or counts");
     if (in->n_rows < 0 || in->n_truth < 0 || in->n_particles < 0) return bad("gtf_truth_build: negative sizes");
     if (in->n_rows > MAX_ROWS || in->n_truth > MAX_ROWS || in->n_particles > MAX_ROWS)
@@ -373,7 +349,7 @@ int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth*
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     if (N == 0) {   // (one stream-ordered fill; nothing to bring back)
-        if ((e = hipMemsetAsync(buf->node_ptr, 0, 4, st)) != hipSuccess) return fail("memset", e);
+        if ((e = hipMemsetAsync(buf->node_ptr, 0, 4, st)) != hipSuccess) return fail(who, "memset", e);
         return 0;
     }
     Build a;
@@ -388,44 +364,42 @@ int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth*
     a.o = *buf;
     a.w = carve(workspace, N, a.NT, NP);
     const Ws& w = a.w;
-    size_t cb;
-#define TRUTH_CK(call, what) do { cb = w.cub_bytes; if ((e = (call)) != hipSuccess) return fail(what, e); } while (0)
-    if ((e = hipMemsetAsync(w.scal, 0, 4 * S_WORDS, st)) != hipSuccess) return fail("memset", e);
+    const gtf::Cub cub{w.cub, st};
+    if ((e = hipMemsetAsync(w.scal, 0, 4 * S_WORDS, st)) != hipSuccess) return fail(who, "memset", e);
     // 1. the high-pT ids
     if (NP > 0) {
         hipLaunchKernelGGL(k_particles, dim3(grid(NP)), dim3(BLOCK), 0, st, a);
-        TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.pk, w.va, w.pf, NP, 0, 64, st), "sort particles");
-        TRUTH_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.pf, w.ps, NP + 1, st), "scan particles");
+        if ((e = cub.sort_pairs(w.ka, w.pk, w.va, w.pf, NP)) != hipSuccess) return fail(who, "sort particles", e);
+        if ((e = cub.scan(w.pf, w.ps, NP + 1)) != hipSuccess) return fail(who, "scan particles", e);
     }
     // 2. the truth rows by hit
     hipLaunchKernelGGL(k_truth_rows, dim3(grid(a.NT)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.tk, w.va, w.tidx, a.NT, 0, 64, st), "sort truth");
+    if ((e = cub.sort_pairs(w.ka, w.tk, w.va, w.tidx, a.NT)) != hipSuccess) return fail(who, "sort truth", e);
     hipLaunchKernelGGL(k_truth_sorted, dim3(grid(a.NT)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.tfs, w.ts, a.NT + 1, st), "scan truth");
+    if ((e = cub.scan(w.tfs, w.ts, a.NT + 1)) != hipSuccess) return fail(who, "scan truth", e);
     // 3. the rows; 4. the region particles
     hipLaunchKernelGGL(k_rows, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kb, w.va, w.vb, N, 0, 64, st), "sort modules");
+    if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.vb, N)) != hipSuccess) return fail(who, "sort modules", e);
     hipLaunchKernelGGL(k_pid_keys, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kb, w.vb, w.va, N, 0, 64, st), "sort region");
+    if ((e = cub.sort_pairs(w.ka, w.kb, w.vb, w.va, N)) != hipSuccess) return fail(who, "sort region", e);
     hipLaunchKernelGGL(k_mark, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in_a, w.sum_a, N + 1, st), "scan heads");
-    TRUTH_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in_b, w.sum_b, N + 1, st), "scan rows");
+    if ((e = cub.scan(w.in_a, w.sum_a, N + 1)) != hipSuccess) return fail(who, "scan heads", e);
+    if ((e = cub.scan(w.in_b, w.sum_b, N + 1)) != hipSuccess) return fail(who, "scan rows", e);
     hipLaunchKernelGGL(k_heads, dim3(grid(N)), dim3(BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_region, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceReduce::Sum(w.cub, cb, w.ref, w.scal + S_REF, N, st), "sum");
+    if ((e = cub.sum(w.ref, w.scal + S_REF, N)) != hipSuccess) return fail(who, "sum", e);
     // 5. the CSR
     hipLaunchKernelGGL(k_node_keys, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kb, w.va, w.vb, N, 0, 64, st), "sort nodes");
+    if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.vb, N)) != hipSuccess) return fail(who, "sort nodes", e);
     hipLaunchKernelGGL(k_hit_keys, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.ka, w.kc, w.va, w.vc, N, 0, 64, st), "sort pairs");
+    if ((e = cub.sort_pairs(w.ka, w.kc, w.va, w.vc, N)) != hipSuccess) return fail(who, "sort pairs", e);
     hipLaunchKernelGGL(k_first, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-    TRUTH_CK(hipcub::DeviceScan::ExclusiveSum(w.cub, cb, w.in_a, w.sum_a, N + 1, st), "scan pairs");
+    if ((e = cub.scan(w.in_a, w.sum_a, N + 1)) != hipSuccess) return fail(who, "scan pairs", e);
     hipLaunchKernelGGL(k_csr, dim3(grid(N)), dim3(BLOCK), 0, st, a);
-#undef TRUTH_CK
-    if ((e = hipGetLastError()) != hipSuccess) return fail("launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
     int32_t c[S_WORDS] = {0, 0, 0, 0, 0};
-    if ((e = hipMemcpyAsync(c, w.scal, sizeof(c), hipMemcpyDeviceToHost, st)) != hipSuccess) return fail("counts", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail("synchronize", e);
+    if ((e = hipMemcpyAsync(c, w.scal, sizeof(c), hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "counts", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "synchronize", e);
     counts->error = (uint32_t)c[S_ERR];
     if (counts->error & GTF_TRUTH_ERR_RANGE)
         return bad("gtf_truth_build: a volume_id, layer_id or module_id outside [0, 2^21)");

@@ -24,11 +24,8 @@
 #include <stdint.h>
 
 #include "../../include/gtf.h"
+#include "gtf_host.h"
 #include "gtf_math.h"
-
-namespace gtf {
-void set_error(const char* msg);
-}
 
 namespace {
 

@@ -199,6 +199,71 @@ def test_run_dev_equals_run(name, mem):
         assert (b.res["gnn"] != b.g.node["gnn"]).any()                   # a merge happened
 
 
+@functools.lru_cache(maxsize=None)
+def guard_input(name):
+    """(graph, vivl): an order graph -- "directed", 257 nodes in one subgraph, or 257 subgraphs of
+    one node (one over a block; the two extremes of n_sub) -- with seeded finite hits, which the
+    order graphs do not carry, and one layer per node, so every candidate of numhits nodes is fitted"""
+    if name == "directed":
+        g = order_graph("directed")
+    elif name == "one":
+        g = graph.pack([oc.subgraph(7, [257], range(5000, 5257), cut=False)])
+    else:
+        g = graph.pack([oc.subgraph(300 + i, [1], [9000 + i]) for i in range(257)])
+    rng = np.random.default_rng(23)
+    N = g.n_nodes
+    r, phi = 30.0 + 900.0 * rng.random(N), rng.uniform(-np.pi, np.pi, N)
+    g = g.copy()
+    g.node["xyzr"] = np.stack([r * np.cos(phi), r * np.sin(phi), rng.normal(0.0, 300.0, N), r], 1)
+    g.node["gnn"] = g.node["xyzr"].copy()
+    return g, np.stack([np.full(N, 8.0), np.arange(N, dtype=np.float64)], 1)
+
+
+@pytest.mark.parametrize("name", ["directed", "one", "singles"])
+def test_extract_candidates_guard_bytes(name):
+    """gtf_extract_candidates, then gtf_extract_outputs reading its member list, on a workspace of
+    exactly gtf_extract_workspace_bytes followed by guard bytes: the guard stays, the results are
+    the host path's"""
+    import torch
+    from gtf.device import DeviceGraph
+    g, vivl = guard_input(name)
+    p = X.extract_params()
+    d = DeviceGraph(g)
+    N, S = g.n_nodes, d.n_sub
+    assert (N, S) == {"directed": (418, 7), "one": (257, 1), "singles": (257, 257)}[name]
+    order = extract.candidate_order(g)
+    exp = extract.run(g, vivl, p, order_key=order, d=d)
+    exp_out = extract.outputs(g, exp, p.numhits, order)
+    nb = int(d.lib.gtf_extract_workspace_bytes(N, S))
+    ws = torch.full((nb + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    full = lambda v, dt, n=N: torch.full((n,), v, dtype=dt, device="cuda")   # noqa: E731
+    t = {"gnn": torch.from_numpy(g.node["gnn"].ravel().copy()).cuda(), "label": full(0, torch.int32),
+         "status": full(-1, torch.int8), "pxy": full(np.nan, torch.float64), "pzr": full(np.nan, torch.float64),
+         "ext": full(0, torch.uint8), "ncand": full(0, torch.int32, 1)}
+    sp, vivl_dev, order_dev = extract.sub_ptr_dev(d), d._dev_from(vivl), d._dev_from(order)
+    io = nat.GtfExtractIO(d.ptr("xyzr"), vp(vivl_dev), d.ptr("sub_id"), vp(sp), S, 0, vp(order_dev), vp(t["gnn"]),
+                          vp(t["label"]), vp(t["status"]), vp(t["pxy"]), vp(t["pzr"]), vp(t["ext"]), vp(t["ncand"]))
+    cp = p.c()
+    rc = d.lib.gtf_extract_candidates(ctypes.byref(d.cg), ctypes.byref(d.ce), ctypes.byref(io), ctypes.byref(cp),
+                                      vp(ws), d.stream)
+    assert rc == 0, d.lib.gtf_last_error()
+    out = extract.outputs_dev(d, {"io": io, "ws": ws}, p.numhits, ids=False)
+    torch.cuda.synchronize()
+    assert bool((ws[nb:] == 0xA5).all())
+    got = {k: v.cpu().numpy() for k, v in t.items()}
+    for k in ("label", "status", "ext"):
+        assert np.array_equal(got[k], exp[k]), k
+    for k in ("pxy", "pzr"):
+        assert _bits(got[k], exp[k]), k
+    assert _bits(got["gnn"].reshape(-1, 4), exp["gnn"])
+    assert int(got["ncand"][0]) == exp["n_candidates"]
+    for k in ("extracted", "remaining", "fragments"):
+        assert _lists_equal(out[k], exp_out[k]), k
+    for k in ("pval_xy", "pval_zr"):
+        assert _bits(out[k], exp_out[k]), k
+
+
 # ---------------------------------------------------------------- outputs
 def test_outputs_cases_reach_their_branches():
     b = both("directed", "torch")
