@@ -12,9 +12,17 @@
 //   fill  up to MAXC columns per launch (the column table in the kernel arguments,
 //         blockIdx.y = column): every 1-, 4- or 8-byte word of the column gets the pattern
 //
+//   window  (gtf_event_window) the parsed node columns of gtf_csv_parse -> the kept rows of
+//         io.read_nodes: lo <= layer_id <= hi, compacted in file order by one exclusive sum of
+//         (kept | ambiguous << 32), with r = sqrt(x*x + y*y) and the list of the nodes whose x*x
+//         or y*y lies so close to a rounding midpoint that the C library's pow(x, 2), which
+//         defines r (io.edge_length_xy), may round the other way; gtf_event_radius_patch
+//         scatters the caller's r of those nodes. One synchronisation, for the two counts.
+//
 // Plain loads, vector stores, consecutive lanes on consecutive destination words; no atomics,
-// no synchronisation, no allocation.
+// no allocation; pack and fill do not synchronise.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -110,9 +118,142 @@ __global__ __launch_bounds__(BLOCK) void k_fill(ColTab tab) {
     else fill_words<uint8_t>(c);
 }
 
+// ---- window ----
+struct WinWs {
+    int64_t *in, *sum;   // [n + 1] kept | ambiguous << 32; the exclusive sum
+    gtf::Scratch cub;
+    size_t total;
+};
+
+WinWs win_carve(void* base, int64_t n) {
+    WinWs w;
+    gtf::Arena a(base);
+    const size_t n1 = (size_t)(n > 0 ? n : 0) + 1;
+    w.in = a.take<int64_t>(n1);
+    w.sum = a.take<int64_t>(n1);
+    w.cub = gtf::CubNeed().scan<int64_t>((int)n1).take(a);
+    w.total = a.used();
+    return w;
+}
+
+struct Win {
+    int32_t n;
+    int64_t lo, hi;
+    const int64_t *ids, *layer_id;
+    const double *x, *y, *z;
+    gtf_window_out o;
+    WinWs w;
+};
+
+// May a pow(v, 2) with a final error of at most 0.5625 ulp differ from the rounded v * v: the exact
+// square p + e (e = fma(v, v, -p), exact) lies within ulp(p) / 16 of the midpoint between p and a
+// neighbour. |e| <= ulp(p) / 2, so that is |e| > 7 / 16 ulp(p); ulp from the exponent bits, so every
+// product below is exact. A square that is not a normal number (0 * 0 aside) is left to the caller.
+__device__ __forceinline__ bool ambiguous_square(double v) {
+    if (v == 0.0) return false;
+    const double p = v * v;
+    const int ex = (int)((uint64_t)__double_as_longlong(p) >> 52) & 0x7ff;
+    if (ex == 0x7ff || ex < 64) return true;   // inf, nan; a square near or below the subnormals
+    const double e = fma(v, v, -p);
+    const double ulp = __longlong_as_double((int64_t)(ex - 52) << 52);
+    return fabs(e) > 0.4375 * ulp;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_window_flags(Win a) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i > a.n) return;
+    int64_t f = 0;
+    if (i < a.n) {
+        const int64_t l = a.layer_id[i];
+        if (l >= a.lo && l <= a.hi) f = 1 | ((int64_t)(ambiguous_square(a.x[i]) || ambiguous_square(a.y[i])) << 32);
+    }
+    a.w.in[i] = f;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_window_scatter(Win a) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const int64_t f = a.w.in[i], s = a.w.sum[i];
+    if (!(f & 1)) return;
+    const int d = (int)(uint32_t)s, k = (int)((uint64_t)s >> 32);
+    if (d < 0 || d >= a.n || k < 0 || k >= a.n) return;
+    const double x = a.x[i], y = a.y[i];
+    a.o.node_idx[d] = a.ids[i];
+    a.o.layer_id[d] = a.layer_id[i];
+    a.o.x[d] = x;
+    a.o.y[d] = y;
+    a.o.z[d] = a.z[i];
+    a.o.r[d] = __dsqrt_rn(x * x + y * y);   // two rounded products, a rounded sum (-ffp-contract=off)
+    if (f >> 32) {
+        a.o.amb_index[k] = d;
+        a.o.amb_x[k] = x;
+        a.o.amb_y[k] = y;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_radius_patch(double* r, int32_t n_nodes, const int32_t* index, const double* value,
+                                                        int32_t n) {
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const int32_t d = index[k];
+    if (d >= 0 && d < n_nodes) r[d] = value[k];
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t gtf_event_window_workspace_bytes(int32_t n_rows) { return win_carve(nullptr, n_rows).total; }
+
+int gtf_event_window(const gtf_window_in* in, const gtf_window_out* out, gtf_window_counts* counts, void* workspace,
+                     size_t workspace_bytes, gtf_stream_t stream) {
+    const char* who = "gtf_event_window";
+    if (int rc = gtf::check_abi(in, who, "gtf_window_in", "gtf_window_in")) return rc;
+    if (!out || !counts) return bad("gtf_event_window: null out or counts");
+    if (in->n_rows < 0) return bad("gtf_event_window: negative n_rows");
+    if (in->n_rows > INT32_MAX / 4) return bad("gtf_event_window: event too large for int32 indices");
+    counts->n_kept = counts->n_ambiguous = 0;
+    const int32_t n = in->n_rows;
+    if (n == 0) return 0;
+    if (!in->node_idx || !in->layer_id || !in->x || !in->y || !in->z)
+        return bad("gtf_event_window: missing input column (node_idx, layer_id, x, y, z)");
+    if (!out->node_idx || !out->layer_id || !out->x || !out->y || !out->z || !out->r || !out->amb_index || !out->amb_x ||
+        !out->amb_y)
+        return bad("gtf_event_window: missing array of gtf_window_out");
+    if (!workspace || workspace_bytes < gtf_event_window_workspace_bytes(n))
+        return bad("gtf_event_window: workspace smaller than gtf_event_window_workspace_bytes");
+    Win a;
+    a.n = n; a.lo = in->lo; a.hi = in->hi;
+    a.ids = in->node_idx; a.layer_id = in->layer_id; a.x = in->x; a.y = in->y; a.z = in->z;
+    a.o = *out;
+    a.w = win_carve(workspace, n);
+    hipStream_t st = (hipStream_t)stream;
+    const gtf::Cub cub{a.w.cub, st};
+    hipError_t e;
+    hipLaunchKernelGGL(k_window_flags, dim3(gtf::grid((int64_t)n + 1)), dim3(BLOCK), 0, st, a);
+    if ((e = cub.scan(a.w.in, a.w.sum, n + 1)) != hipSuccess) return fail(who, "scan", e);
+    hipLaunchKernelGGL(k_window_scatter, dim3(gtf::grid(n)), dim3(BLOCK), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
+    int64_t total = 0;
+    if ((e = hipMemcpyAsync(&total, a.w.sum + n, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "counts", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "synchronize", e);
+    const int64_t kept = (int64_t)(uint32_t)total, amb = (int64_t)((uint64_t)total >> 32);
+    if (kept > n || amb > kept) return bad("gtf_event_window: inconsistent counts");
+    counts->n_kept = (int32_t)kept;
+    counts->n_ambiguous = (int32_t)amb;
+    return 0;
+}
+
+int gtf_event_radius_patch(double* r, int32_t n_nodes, const int32_t* index, const double* value, int32_t n,
+                           gtf_stream_t stream) {
+    if (n_nodes < 0 || n < 0) return bad("gtf_event_radius_patch: negative sizes");
+    if (n == 0) return 0;
+    if (!r || !index || !value) return bad("gtf_event_radius_patch: null r, index or value with n > 0");
+    hipLaunchKernelGGL(k_radius_patch, dim3(gtf::grid(n)), dim3(BLOCK), 0, (hipStream_t)stream, r, n_nodes, index, value, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("gtf_event_radius_patch", "launch", e);
+    return 0;
+}
 
 int gtf_event_pack(const gtf_event_csr* ev, const gtf_event_cols* in, const gtf_event_out* out, gtf_stream_t stream) {
     const char* who = "gtf_event_pack";

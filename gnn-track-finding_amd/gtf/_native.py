@@ -217,6 +217,61 @@ class GtfFillColumn(ctypes.Structure):
 FILL_MAX_COLUMNS = 32   # GTF_FILL_MAX_COLUMNS
 
 
+CSV_MAX_COLUMNS, CSV_MAX_FIELDS, CSV_MAX_ROW_BYTES = 16, 64, 1024   # GTF_CSV_MAX_*
+CSV_INT64, CSV_DOUBLE = 0, 1                                        # GTF_CSV_INT64 / _DOUBLE
+# GTF_CSV_ERR_*
+(CSV_ERR_DIGITS, CSV_ERR_EXPONENT, CSV_ERR_TEXT, CSV_ERR_EMPTY, CSV_ERR_QUOTE, CSV_ERR_SPACE, CSV_ERR_INT_FORM,
+ CSV_ERR_FIELDS, CSV_ERR_ROW_LONG, CSV_ERR_ROWS) = (1 << k for k in range(10))
+CSV_ERRORS = {CSV_ERR_DIGITS: "more digits than the exact domain holds", CSV_ERR_EXPONENT: "decimal exponent beyond 22",
+              CSV_ERR_TEXT: "not a number", CSV_ERR_EMPTY: "empty field", CSV_ERR_QUOTE: "quoted field",
+              CSV_ERR_SPACE: "space or tab inside a field", CSV_ERR_INT_FORM: "point or exponent in an integer column",
+              CSV_ERR_FIELDS: "wrong number of fields", CSV_ERR_ROW_LONG: "row longer than 1024 bytes",
+              CSV_ERR_ROWS: "more rows than max_rows"}
+
+
+class GtfCsvColumn(ctypes.Structure):
+    """gtf_csv_column: one requested field of gtf_csv_parse"""
+    _fields_ = [("field", I32), ("type", I32), ("out", P)]
+
+
+class GtfCsvIn(ctypes.Structure):
+    """gtf_csv_in; keyword construction only -- struct_size / abi_version are filled in"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("text", P), ("n_bytes", I32), ("skip_lines", I32),
+                ("n_fields", I32), ("max_rows", I32), ("n_columns", I32), ("delimiter", ctypes.c_uint8),
+                ("pad_", ctypes.c_uint8 * 3), ("columns", GtfCsvColumn * CSV_MAX_COLUMNS)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfCsvIn)
+        self.abi_version = ABI_VERSION
+
+
+class GtfCsvCounts(ctypes.Structure):
+    _fields_ = [("n_rows", I32), ("error", U32), ("first_bad_row", I32), ("first_bad_field", I32),
+                ("first_bad_error", U32), ("pad_", I32)]
+
+
+class GtfWindowIn(ctypes.Structure):
+    """gtf_window_in; keyword construction only -- struct_size / abi_version are filled in"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_rows", I32), ("pad_", I32), ("lo", ctypes.c_int64),
+                ("hi", ctypes.c_int64), ("node_idx", P), ("layer_id", P), ("x", P), ("y", P), ("z", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfWindowIn)
+        self.abi_version = ABI_VERSION
+
+
+class GtfWindowOut(ctypes.Structure):
+    """gtf_window_out: the caller-allocated outputs of gtf_event_window, each [n_rows]"""
+    _fields_ = [("node_idx", P), ("layer_id", P), ("x", P), ("y", P), ("z", P), ("r", P), ("amb_index", P),
+                ("amb_x", P), ("amb_y", P)]
+
+
+class GtfWindowCounts(ctypes.Structure):
+    _fields_ = [("n_kept", I32), ("n_ambiguous", I32)]
+
+
 class GtfCandidateGraph(ctypes.Structure):
     _fields_ = [("n_nodes", I32), ("n_slots", I32), ("n_edges", I32), ("pad_", I32), ("slot_ptr", P),
                 ("slot_src", P), ("is_edge", P), ("act", P), ("out_ptr", P), ("out_slot", P), ("sub_id", P),
@@ -286,6 +341,8 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
            "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_event_pack", "gtf_fill_columns",
+           "gtf_csv_chunk_bytes", "gtf_csv_parse_workspace_bytes", "gtf_csv_parse",
+           "gtf_event_window_workspace_bytes", "gtf_event_window", "gtf_event_radius_patch",
            "gtf_updated_state_pair_counts", "gtf_updated_state_distances", "gtf_set_diagnostics",
            "gtf_device_init", "gtf_malloc", "gtf_free", "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod",
            "gtf_memset", "gtf_stream_synchronize",
@@ -403,6 +460,16 @@ def lib(lean: bool = False):
     L.gtf_event_pack.argtypes = [ctypes.POINTER(GtfEventCsr), ctypes.POINTER(GtfEventCols),
                                  ctypes.POINTER(GtfEventOut), P]
     L.gtf_fill_columns.argtypes = [ctypes.POINTER(GtfFillColumn), I32, P]
+    L.gtf_csv_chunk_bytes.restype = ctypes.c_size_t
+    L.gtf_csv_chunk_bytes.argtypes = []
+    L.gtf_csv_parse_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_csv_parse_workspace_bytes.argtypes = [I32]
+    L.gtf_csv_parse.argtypes = [ctypes.POINTER(GtfCsvIn), ctypes.POINTER(GtfCsvCounts), P, ctypes.c_size_t, P]
+    L.gtf_event_window_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_event_window_workspace_bytes.argtypes = [I32]
+    L.gtf_event_window.argtypes = [ctypes.POINTER(GtfWindowIn), ctypes.POINTER(GtfWindowOut),
+                                   ctypes.POINTER(GtfWindowCounts), P, ctypes.c_size_t, P]
+    L.gtf_event_radius_patch.argtypes = [P, I32, P, P, I32, P]
     L.gtf_candidate_order.argtypes = [ctypes.POINTER(GtfCandidateGraph), P]
     L.gtf_updated_state_pair_counts.argtypes = [G, N, S, E, P, P]
     L.gtf_updated_state_distances.argtypes = [G, N, S, E, P, P, ctypes.POINTER(GtfPairOut), P]
@@ -441,7 +508,8 @@ def lib(lean: bool = False):
                "gtf_tag_propagate_shard", "gtf_graph_prepare", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
                "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
                "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
-               "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build"):
+               "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
+               "gtf_event_radius_patch"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

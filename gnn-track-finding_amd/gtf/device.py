@@ -992,7 +992,9 @@ class DeviceGraph:
         """The packed event of gtf.io.build_event_csr (event_conversion.py:53-101, helper.py:465-545),
         made in HBM: host columns of the nodes kept by the volume window, in CSV order (io.read_nodes),
         and the edge rows as io.csr_from_rows takes them (add_edge(row_a, row_b) first). The eight
-        columns go up once; gtf_build_event_csr_device builds the CSR, gtf_event_pack the node columns,
+        columns go up once -- or are device arrays of this allocator already (gtf.io.read_nodes_dev /
+        read_edges_dev: int64 ids, layer_id >= 0 and rows, float64 coordinates; nothing is uploaded and
+        N and R are their lengths) --; gtf_build_event_csr_device builds the CSR, gtf_event_pack the node columns,
         gtf_fill_columns the empty states (every edge active, has_tse set) and gtf_graph_prepare the
         schedules and slot tables. Natural layout, tables == "device"; the node ids are the resident
         node_id column (node_id_dev, subset) and vivl is ``carried["vivl"]``. host_graph() downloads it."""
@@ -1004,14 +1006,23 @@ class DeviceGraph:
         been issued (tools/resident_event.py synchronises and reads the clock there)"""
         if mem not in ("torch", "hip"):
             raise ValueError("mem must be 'torch' or 'hip'")
-        ids, layer_id, row_a, row_b = (np.ascontiguousarray(a, np.int64).reshape(-1)
-                                       for a in (ids, layer_id, row_a, row_b))
-        x, y, z, r = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (x, y, z, r))
-        N, R = int(ids.size), int(row_a.size)
-        if any(a.size != N for a in (x, y, z, r, layer_id)) or row_b.size != R:
-            raise ValueError("from_event: one x, y, z, r and layer_id per node id, one row_b per row_a")
-        if N and int(layer_id.min()) < 0:
-            raise ValueError("from_event: negative layer_id")
+        on_dev = hasattr(ids, "data_ptr")   # device columns (gtf.io.read_nodes_dev / read_edges_dev)
+        if on_dev:
+            given = (ids, row_a, row_b, x, y, z, r, layer_id)
+            if not all(hasattr(a, "data_ptr") for a in given):
+                raise ValueError("from_event: the eight columns are all host arrays or all device arrays")
+            N, R = int(ids.numel()), int(row_a.numel())
+            if any(int(a.numel()) != N for a in (x, y, z, r, layer_id)) or int(row_b.numel()) != R:
+                raise ValueError("from_event: one x, y, z, r and layer_id per node id, one row_b per row_a")
+        else:
+            ids, layer_id, row_a, row_b = (np.ascontiguousarray(a, np.int64).reshape(-1)
+                                           for a in (ids, layer_id, row_a, row_b))
+            x, y, z, r = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (x, y, z, r))
+            N, R = int(ids.size), int(row_a.size)
+            if any(a.size != N for a in (x, y, z, r, layer_id)) or row_b.size != R:
+                raise ValueError("from_event: one x, y, z, r and layer_id per node id, one row_b per row_a")
+            if N and int(layer_id.min()) < 0:
+                raise ValueError("from_event: negative layer_id")
         c = cls.__new__(cls)
         c.mem = mem
         c.torch = torch = _torch() if mem == "torch" else None
@@ -1030,8 +1041,8 @@ class DeviceGraph:
         L, vp = c.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
         E = n_sub = 0
         if N:
-            up = {k: c._dev_from(a) for k, a in (("ids", ids), ("a", row_a), ("b", row_b), ("x", x), ("y", y),
-                                                 ("z", z), ("r", r), ("layer_id", layer_id))}
+            up = {k: a if on_dev else c._dev_from(a) for k, a in (("ids", ids), ("a", row_a), ("b", row_b), ("x", x),
+                                                                  ("y", y), ("z", z), ("r", r), ("layer_id", layer_id))}
             mark("upload")
             csr = {k: c._dev_empty(n, np.int32) for k, n in (("order", N), ("sub_id", N), ("slot_ptr", N + 1),
                                                               ("slot_src", 2 * R), ("tse_rank", 2 * R),

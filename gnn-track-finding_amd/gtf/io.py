@@ -53,6 +53,78 @@ def read_edges(path: str):
     return e[:, 0].astype(np.int64), e[:, 1].astype(np.int64)
 
 
+class DeviceNodes:
+    """read_nodes_dev's result: read_nodes's six columns as device arrays of ``n`` elements (``ids``,
+    ``x``, ``y``, ``z``, ``r``, ``layer_id``), ``n_rows`` (the file's rows), ``n_ambiguous`` (the
+    nodes whose r came from edge_length_xy on the host) and ``r_unpatched`` (keep_unpatched=True: r
+    as gtf_event_window left it). host() downloads read_nodes's tuple."""
+
+    def __init__(self, mm, cols, n, n_rows, n_ambiguous, r_unpatched=None):
+        self._m, self.n, self.n_rows, self.n_ambiguous, self.r_unpatched = mm, n, n_rows, n_ambiguous, r_unpatched
+        self.ids, self.x, self.y, self.z, self.r, self.layer_id = cols
+
+    def host(self):
+        return tuple(self._m.host(a, self.n, dt) for a, dt in
+                     ((self.ids, np.int64), (self.x, np.float64), (self.y, np.float64), (self.z, np.float64),
+                      (self.r, np.float64), (self.layer_id, np.int64)))
+
+
+def read_nodes_dev(data_or_path, min_volume: int, max_volume: int, device="cuda", mem: str = "torch", mark=None,
+                   keep_unpatched: bool = False) -> DeviceNodes:
+    """read_nodes on the device: gtf_csv_parse (gtf.csvdev.parse_dev) for node_idx, layer_id, x, y, z
+    by header name, gtf_event_window for the volume window and r = sqrt(x*x + y*y). The definition of
+    r squares through the C library's pow (edge_length_xy), which is not always x * x: the window
+    also lists the nodes where the two can differ, edge_length_xy -- the definition itself -- runs on
+    the host for just those, and gtf_event_radius_patch writes its results over r. The same six
+    arrays as read_nodes, bit for bit. Raises csvdev.OutOfDomain for a field outside the parser's
+    exact domain. mark: called with "upload", "parse", "window", "patch" as each part is done."""
+    import ctypes
+    from . import _native as nat
+    from . import csvdev
+    from .metrics import _Mem
+    if min_volume < 0:
+        raise ValueError("read_nodes_dev: negative min_volume")
+    mark = mark or (lambda part: None)
+    mm = _Mem(device, mem)
+    c = csvdev.parse_dev(data_or_path, (("node_idx", "int64"), ("layer_id", "int64"), ("x", "float64"),
+                                        ("y", "float64"), ("z", "float64")), 1, mm=mm, mark=mark)
+    n = c.n_rows
+    m1 = max(n, 1)
+    out = [mm.empty(m1, dt) for dt in (np.int64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int32,
+                                       np.float64, np.float64)]
+    win = nat.GtfWindowIn(n_rows=n, lo=min_volume * 1000, hi=(max_volume + 1) * 1000,
+                          **{k: mm.p(c[k]) for k in ("node_idx", "layer_id", "x", "y", "z")})
+    wout = nat.GtfWindowOut(*(mm.p(a) for a in out))
+    nb = int(mm.lib.gtf_event_window_workspace_bytes(n))
+    ws = mm.empty(nb, np.uint8)
+    cnt = nat.GtfWindowCounts()
+    nat.check(mm.lib.gtf_event_window(ctypes.byref(win), ctypes.byref(wout), ctypes.byref(cnt), mm.p(ws),
+                                      ctypes.c_size_t(nb), mm.stream))
+    mark("window")
+    kept, amb = int(cnt.n_kept), int(cnt.n_ambiguous)
+    ids, lay, x, y, z, r = (mm.first(a, kept) for a in out[:6])
+    raw = None
+    if keep_unpatched:
+        raw = mm.host(r, kept, np.float64).copy()
+    if amb:
+        ax, ay = mm.host(out[7], amb, np.float64), mm.host(out[8], amb, np.float64)
+        val = mm.from_host(edge_length_xy(ax, ay))
+        nat.check(mm.lib.gtf_event_radius_patch(mm.p(r), kept, mm.p(out[6]), mm.p(val), amb, mm.stream))
+        if mm.torch is None:    # (val is freed at once: a plain allocation is not stream-ordered)
+            nat.check(mm.lib.gtf_stream_synchronize(None))
+    mark("patch")
+    return DeviceNodes(mm, (ids, x, y, z, r, lay), kept, n, amb, raw)
+
+
+def read_edges_dev(data_or_path, device="cuda", mem: str = "torch"):
+    """read_edges on the device: fields 0 and 1 of edges.csv after its two leading lines, read as
+    int64 directly (np.loadtxt reads floats and casts: an id written "960.0" is outside the domain,
+    csvdev.OutOfDomain). Returns (node2, node1, rows), device arrays."""
+    from . import csvdev
+    c = csvdev.parse_dev(data_or_path, ((0, "int64"), (1, "int64")), 2, device, mem)
+    return c[0], c[1], c.n_rows
+
+
 def load_event(event_prefix: str, min_volume: int, max_volume: int, params=None) -> TrackGraph:
     """``event_prefix`` like ``.../event_1_filtered_graph_`` (nodes.csv / edges.csv appended)."""
     from .synth import _assemble

@@ -318,35 +318,42 @@ class DeviceTruth:
 def truth_tables_dev(m: HitMapping, particle_id, px, py, min_volume: int, max_volume: int, truth_hit_id=None,
                      truth_particle_id=None, device="cuda", mem: str = "torch") -> DeviceTruth:
     """truth_tables on the device (gtf_truth_build, csrc/gtf_truth.hip): the columns go up once
-    and the six arrays stay there, array_equal to the host function's. The mapping's volume_id,
+    and the six arrays stay there, array_equal to the host function's. Any column may be a device
+    array of this allocator already (int64 ids, float64 px / py: gtf.csvdev.parse_dev, truth_files_dev);
+    it is used where it is. The mapping's volume_id,
     layer_id and module_id must lie in [0, 2^21) (ValueError); a mapped hit without a truth row
     is the host's ValueError."""
     from . import _native as nat
     mm = _Mem(device, mem)
-    cols = [np.ascontiguousarray(getattr(m, c), np.int64).reshape(-1) for c in
-            ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id")]
-    n = int(cols[0].size)
-    if any(c.size != n for c in cols):
+
+    def col(a, dt):   # a host column (uploaded below) or a device array as it is
+        return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dt).reshape(-1)
+
+    def size(a):
+        return int(a.numel()) if hasattr(a, "data_ptr") else int(a.size)
+
+    cols = [col(getattr(m, c), np.int64) for c in ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id")]
+    n = size(cols[0])
+    if any(size(c) != n for c in cols):
         raise ValueError("mapping columns of different lengths")
     truth = []
     if truth_hit_id is not None:
-        truth = [np.ascontiguousarray(a, np.int64).reshape(-1) for a in (truth_hit_id, truth_particle_id)]
-        if truth[0].size != truth[1].size:
+        truth = [col(a, np.int64) for a in (truth_hit_id, truth_particle_id)]
+        if size(truth[0]) != size(truth[1]):
             raise ValueError("truth columns of different lengths")
-        if truth[0].size == 0:      # (for the library n_truth == 0 means "the mapping's own columns")
+        if size(truth[0]) == 0:      # (for the library n_truth == 0 means "the mapping's own columns")
             if n:
                 raise ValueError("a mapped hit has no truth row (helper.__get_particle_id .item())")
             truth = []
-    part = [np.ascontiguousarray(particle_id, np.int64).reshape(-1), np.ascontiguousarray(px, np.float64).reshape(-1),
-            np.ascontiguousarray(py, np.float64).reshape(-1)]
-    if not part[0].size == part[1].size == part[2].size:
+    part = [col(particle_id, np.int64), col(px, np.float64), col(py, np.float64)]
+    if not size(part[0]) == size(part[1]) == size(part[2]):
         raise ValueError("particle columns of different lengths")
-    n_truth, n_part = int(truth[0].size) if truth else 0, int(part[0].size)
+    n_truth, n_part = size(truth[0]) if truth else 0, size(part[0])
     if min_volume > max_volume:
         raise ValueError("min_volume > max_volume")
     if max(n, n_truth, n_part) > 1 << 30:
         raise ValueError("more than 2^30 rows")
-    dev = [mm.from_host(a) if a.size else None for a in cols + truth + part]
+    dev = [(a if hasattr(a, "data_ptr") else mm.from_host(a)) if size(a) else None for a in cols + truth + part]
     d_truth = dev[6:8] if truth else [None, None]
     names = ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id", "truth_hit", "truth_part",
              "part_id", "px", "py")
@@ -367,6 +374,39 @@ def truth_tables_dev(m: HitMapping, particle_id, px, py, min_volume: int, max_vo
         raise ValueError("a mapped hit has no truth row (helper.__get_particle_id .item())")
     nat.check(rc)
     return DeviceTruth(mm, out, t, cnt)
+
+
+MAPPING_COLUMNS = ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id")
+
+
+def truth_files_dev(prefix: str, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch"):
+    """truth_tables_dev from the files reconstruction_efficiency.score reads (``prefix`` +
+    "particles.csv", + ``mapping``, and + "truth.csv" where it exists), each parsed on the device
+    (gtf.csvdev.parse_dev) with its columns chosen by header name, whatever else the file holds. A
+    file with a field outside the parser's exact domain is read with pd.read_csv instead. Returns
+    (DeviceTruth, {"particles" | "mapping" | "truth": "device" | "host"})."""
+    import os
+    from .csvdev import OutOfDomain, parse_dev
+    mm = _Mem(device, mem)
+    info = {}
+
+    def read(key, path, columns):
+        try:
+            c = parse_dev(path, columns, 1, mm=mm)
+            info[key] = "device"
+            return [c[name] for name, _ in columns]
+        except OutOfDomain as e:
+            import pandas as pd
+            info[key], info[key + "_reason"] = "host", str(e)
+            f = pd.read_csv(path, usecols=[name for name, _ in columns])
+            return [f[name].to_numpy(np.dtype(t)) for name, t in columns]
+
+    pid, px, py = read("particles", prefix + "particles.csv", (("particle_id", "int64"), ("px", "float64"), ("py", "float64")))
+    m = HitMapping(*read("mapping", prefix + mapping, tuple((c, "int64") for c in MAPPING_COLUMNS)))
+    th = tp = None
+    if os.path.isfile(prefix + "truth.csv"):
+        th, tp = read("truth", prefix + "truth.csv", (("hit_id", "int64"), ("particle_id", "int64")))
+    return truth_tables_dev(m, pid, px, py, min_volume, max_volume, th, tp, device, mem), info
 
 
 class DeviceScorer:

@@ -113,19 +113,50 @@ def build_event(event_prefix: str, min_volume: int, max_volume: int, p: Params =
 
 
 def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Params = None, device="cuda",
-                    mem: str = "torch"):
+                    mem: str = "torch", parse: str = "host"):
     """build_event (event_conversion.py:53-101) without its host round trips: the parsed CSV columns go
     up once and the packed network, its empty states and its tables are made in HBM
     (DeviceGraph.from_event: gtf_build_event_csr_device, gtf_event_pack, gtf_fill_columns,
     gtf_graph_prepare); the states, priors, mixture weights, degrees and send weights are computed on
     that object. Returns the DeviceGraph: run(d, None, resident="device") starts iteration 1 on it,
-    d.host_graph() downloads what build_event returns."""
+    d.host_graph() downloads what build_event returns.
+    parse: "host" (io.read_nodes / read_edges, the definition) or "device": the files' bytes go up and
+    gtf_csv_parse, gtf_event_window and gtf_event_radius_patch make the same columns there
+    (io.read_nodes_dev / read_edges_dev). A file with a field outside the device parser's exact
+    domain (csvdev.OutOfDomain) is read by the host reader instead; ``d.parse_info`` says which
+    parser read each file ({"nodes": "device" | "host", "edges": ...}, with "nodes_reason" /
+    "edges_reason" after a fallback). The same graph either way, bit for bit."""
     from . import io
     from .device import DeviceGraph
     p = p or Params()
-    ids, x, y, z, r, layer = io.read_nodes(event_prefix + "nodes.csv", min_volume, max_volume)
-    n2, n1 = io.read_edges(event_prefix + "edges.csv")
+    if parse not in ("host", "device"):
+        raise ValueError("parse must be 'host' or 'device'")
+    info = {"nodes": "host", "edges": "host"}
+    if parse == "host":
+        ids, x, y, z, r, layer = io.read_nodes(event_prefix + "nodes.csv", min_volume, max_volume)
+        n2, n1 = io.read_edges(event_prefix + "edges.csv")
+    else:
+        from .csvdev import OutOfDomain
+        from .metrics import _Mem
+        mm = _Mem(device, mem)
+        try:
+            nd = io.read_nodes_dev(event_prefix + "nodes.csv", min_volume, max_volume, device, mem)
+            ids, x, y, z, r, layer = nd.ids, nd.x, nd.y, nd.z, nd.r, nd.layer_id
+            info["nodes"] = "device"
+        except OutOfDomain as e:
+            info["nodes_reason"] = str(e)
+            host = io.read_nodes(event_prefix + "nodes.csv", min_volume, max_volume)
+            if host[0].size and int(host[5].min()) < 0:
+                raise ValueError("from_event: negative layer_id")
+            ids, x, y, z, r, layer = (mm.from_host(a) for a in host)
+        try:
+            n2, n1, _ = io.read_edges_dev(event_prefix + "edges.csv", device, mem)
+            info["edges"] = "device"
+        except OutOfDomain as e:
+            info["edges_reason"] = str(e)
+            n2, n1 = (mm.from_host(a) for a in io.read_edges(event_prefix + "edges.csv"))
     d = DeviceGraph.from_event(ids, x, y, z, r, layer, n1, n2, device, mem)
+    d.parse_info = info
     if d.n_nodes == 0:
         return d
     d.clear_errors()

@@ -24,6 +24,10 @@ metrics.json comes from gtf.metrics.DeviceScorer, fed each iteration's candidate
 gtf_extract_outputs left them, instead of from the saved lists. The same values.
 --resident-truth (implies --resident-metrics) also builds the scorer's truth tables on the GPU
 (gtf.metrics.truth_tables_dev) from the parsed truth files. The same metrics.json, byte for byte.
+--resident-parse (implies --resident-event) also parses the event's CSV files on the GPU (gtf_csv_parse;
+pipeline.build_event_dev(parse="device")) and, with --resident-truth, the truth files
+(gtf.metrics.truth_files_dev). One line per file says which parser read it: a file with a field outside
+the device parser's exact domain is read by the host reader. The same files either way.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -64,12 +68,22 @@ class _Scorers:
         self.last.add(cand_ptr, cand_ids, n_cand, 0, **kw)
 
 
+def _parser_line(key, info):
+    print("parse %s: %s%s" % (key, info[key], " (%s)" % info[key + "_reason"] if key + "_reason" in info else ""))
+
+
 def _scorers(args):
     """the truth files as reconstruction_efficiency.score reads them -> the two device scorers"""
     import numpy as np
-    import pandas as pd
     from gtf import metrics
     pre = os.path.join(args.truth, "event000001000-")
+    if args.resident_parse and args.resident_truth:
+        tables, info = metrics.truth_files_dev(pre, args.mapping, args.min_volume, args.max_volume, args.device)
+        for key in ("particles", "mapping", "truth"):
+            if key in info:
+                _parser_line(key, info)
+        return _Scorers(tables, args.device)
+    import pandas as pd
     particles = pd.read_csv(pre + "particles.csv")
     m = metrics.HitMapping.from_frame(pd.read_csv(pre + args.mapping))
     th = tp = None
@@ -117,11 +131,16 @@ def main(argv=None):
     ap.add_argument("--resident-truth", action="store_true",
                     help="as --resident-metrics, and the scorer's truth tables are built on the GPU too "
                          "(gtf.metrics.truth_tables_dev); only with --start 1")
+    ap.add_argument("--resident-parse", action="store_true",
+                    help="as --resident-event, and the CSV files are parsed on the GPU (gtf_csv_parse); with "
+                         "--resident-truth the truth files as well; only with --start 1")
     ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
     if args.start < 1 or args.end < args.start:
         ap.error("need 1 <= start <= end")
+    if args.resident_parse:
+        args.resident_event = True
     if args.resident_event and args.start != 1:
         ap.error("--resident-event converts the event: only with --start 1")
     if args.resident_truth:
@@ -140,7 +159,11 @@ def main(argv=None):
         t0 = time.perf_counter()
         prefix = os.path.join(args.eventNetwork, "event_1_filtered_graph_")
         if args.resident_event:
-            dev = pipeline.build_event_dev(prefix, args.min_volume, args.max_volume, p, args.device)
+            dev = pipeline.build_event_dev(prefix, args.min_volume, args.max_volume, p, args.device,
+                                           parse="device" if args.resident_parse else "host")
+            if args.resident_parse:
+                for key in ("nodes", "edges"):
+                    _parser_line(key, dev.parse_info)
             g, vivl = dev.host_graph()   # (the saved file; the loop starts on the resident object)
         else:
             g, vivl = pipeline.build_event(prefix, args.min_volume, args.max_volume, p, args.device)

@@ -35,6 +35,10 @@
  *                       majority particles, the three tests, the match order and its counts)
  *   gtf_truth_build  -> src/extract/reconstruction_efficiency.py:41-91 (the reference tracks) and
  *                       utilities/helper.py:466-479 (hit_dissociation): the scorer's static tables
+ *   gtf_csv_parse    -> the pd.read_csv / np.loadtxt calls in front of both
+ *                       (utilities/helper.py:524-543, reconstruction_efficiency.py:41-47)
+ *   gtf_event_window, gtf_event_radius_patch
+ *                    -> utilities/helper.py:526-531 (the volume window) and :12-13 (r)
  */
 #ifndef GTF_H
 #define GTF_H
@@ -1104,6 +1108,153 @@ typedef struct gtf_fill_column {
  * row_bytes that is neither 1, 4 nor a multiple of 8, a NULL dst with rows > 0, a dst not
  * aligned to its words. */
 int gtf_fill_columns(const gtf_fill_column* cols, int32_t n_cols, gtf_stream_t stream);
+
+/* ---- the CSV files themselves: gtf_csv_parse -------------------------------------------
+ * The front of event conversion and of the scorer (helper.py:524-543 load_nodes_edges,
+ * reconstruction_efficiency.py:41-47: pd.read_csv / np.loadtxt): the bytes of one file in DEVICE
+ * memory to selected fields as int64 or double DEVICE columns in row order. gtf_csv.hip.
+ *
+ * Lines end in "\n" or "\r\n"; the last one may lack it. Blank lines (nothing, or a lone "\r")
+ * are skipped and are neither rows nor skipped lines (pandas skip_blank_lines). The first
+ * skip_lines non-blank lines are not parsed (1: a header; 2: edges.csv, "<N> <E>" and the
+ * header); the caller, who holds the file, resolves header names to field indices. Every row
+ * must have exactly n_fields fields of at most GTF_CSV_MAX_ROW_BYTES bytes in all (the line end
+ * not counted). Fields that no column asks for are split but not read.
+ *
+ * A requested field is [+-]digits[.digits][(e|E)[+-]digits] with at least one mantissa digit
+ * ("5." and ".5" are numbers) and must lie in the exact domain:
+ *   GTF_CSV_INT64   a sign and at most 18 digits, no point, no exponent;
+ *   GTF_CSV_DOUBLE  at most 15 mantissa digit characters (leading zeros count, as they do in
+ *                   pandas' converter) and a net decimal exponent e = written exponent - digits
+ *                   after the point with |e| <= 22; a zero mantissa with any exponent.
+ * The value is then M * 10^e (e >= 0) or M / 10^-e: an exact integer, an exact power of ten and
+ * ONE correctly rounded fp64 operation, the sign applied by negation ("-0" is -0.0): what
+ * pandas.read_csv, np.loadtxt and strtod give, bit for bit. Anything else is not guessed: its
+ * GTF_CSV_ERR_* bit is set in counts->error and the first offending (row, field) -- the lowest
+ * row, then the lowest field -- is reported with its own bit. */
+#define GTF_CSV_MAX_COLUMNS 16
+#define GTF_CSV_MAX_FIELDS 64
+#define GTF_CSV_MAX_ROW_BYTES 1024
+#define GTF_CSV_INT64 0
+#define GTF_CSV_DOUBLE 1
+
+#define GTF_CSV_ERR_DIGITS   0x001u  /* more digits than the domain holds */
+#define GTF_CSV_ERR_EXPONENT 0x002u  /* |e| > 22 with a nonzero mantissa */
+#define GTF_CSV_ERR_TEXT     0x004u  /* nan, inf, text: not the number grammar */
+#define GTF_CSV_ERR_EMPTY    0x008u  /* an empty requested field */
+#define GTF_CSV_ERR_QUOTE    0x010u  /* a '"' in any field of a row, requested or not */
+#define GTF_CSV_ERR_SPACE    0x020u  /* a space or tab inside a requested field */
+#define GTF_CSV_ERR_INT_FORM 0x040u  /* a point or an exponent in an int64 column */
+#define GTF_CSV_ERR_FIELDS   0x080u  /* not n_fields fields: reported at the first missing or extra field */
+#define GTF_CSV_ERR_ROW_LONG 0x100u  /* a row of more than GTF_CSV_MAX_ROW_BYTES bytes: field 0, nothing else of it */
+#define GTF_CSV_ERR_ROWS     0x200u  /* more than max_rows rows: row max_rows, field 0 */
+
+typedef struct gtf_csv_column {
+    int32_t field;               /* [0, n_fields); no two columns ask for the same field */
+    int32_t type;                /* GTF_CSV_INT64 or GTF_CSV_DOUBLE */
+    void* out;                   /* [max_rows] int64_t or double, device, 8-byte aligned */
+} gtf_csv_column;
+
+typedef struct gtf_csv_in {
+    uint32_t struct_size;        /* sizeof(gtf_csv_in) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    const char* text;            /* [n_bytes] the file, device, 16-byte aligned */
+    int32_t n_bytes;             /* < 2^31 - 16 KiB */
+    int32_t skip_lines;          /* non-blank lines in front of the rows */
+    int32_t n_fields;            /* [1, GTF_CSV_MAX_FIELDS]: every row has exactly this many */
+    int32_t max_rows;            /* any upper bound of the row count (newlines + 1): the outputs' size */
+    int32_t n_columns;           /* [0, GTF_CSV_MAX_COLUMNS] */
+    uint8_t delimiter;           /* ',' ; not a character of the number grammar, '"', a line end or 0 */
+    uint8_t pad_[3];
+    gtf_csv_column columns[GTF_CSV_MAX_COLUMNS];
+} gtf_csv_in;
+
+typedef struct gtf_csv_counts {
+    int32_t n_rows;              /* rows parsed (at most max_rows) */
+    uint32_t error;              /* GTF_CSV_ERR_* of every offending field */
+    int32_t first_bad_row;       /* -1 without an error; rows count from 0 after the skipped lines */
+    int32_t first_bad_field;
+    uint32_t first_bad_error;    /* the one bit of that field */
+    int32_t pad_;
+} gtf_csv_counts;
+
+/* The bytes one block takes (4096): a row belongs to the chunk its first byte lies in. */
+size_t gtf_csv_chunk_bytes(void);
+
+/* Scratch of gtf_csv_parse: positive for 0 bytes, non-decreasing; about 8 bytes per chunk. */
+size_t gtf_csv_parse_workspace_bytes(int32_t n_bytes);
+
+/* Two launches around one hipCUB exclusive sum (line starts per chunk; the rows from LDS), no
+ * atomic but the error word's and the first-error key's on a violation, nothing allocated.
+ * Synchronises `stream` once, to fill *counts. Nothing is written past out[n_rows] of a column.
+ * Returns -2 with counts->error set when a field lies outside the domain (the columns are then
+ * unspecified); -3 for another ABI of *in; -2, decided on the host before any launch, for a null
+ * argument, negative sizes, a text that is too large or not aligned, n_fields or n_columns out of
+ * range, a refused delimiter, a column whose field is out of range or asked for twice, whose type is
+ * unknown or whose output is null (max_rows > 0) or unaligned, or a small workspace. n_bytes == 0:
+ * returns 0 with zero counts, nothing launched, no workspace needed. */
+int gtf_csv_parse(const gtf_csv_in* in, gtf_csv_counts* counts, void* workspace, size_t workspace_bytes,
+                  gtf_stream_t stream);
+
+/* ---- parsed node columns -> the columns of gtf_event_cols: gtf_event_window -------------
+ * gtf/io.py read_nodes after the parse (helper.py:524-531): the rows with lo <= layer_id <= hi,
+ * both ends inclusive, compacted in file order, and r = sqrt(x*x + y*y) in fp64.
+ *
+ * r is DEFINED through the C library's pow(x, 2) (helper.py:12-13, gtf/io.py edge_length_xy),
+ * which is not always the rounded x * x and differs between C libraries, so it is not ported.
+ * Instead the call lists the kept nodes where the two may differ: with p = x * x rounded and
+ * e = fma(x, x, -p) the exact residual, a node is AMBIGUOUS when, for its x or its y,
+ * | |e| - ulp(p) / 2 | < ulp(p) / 16 -- every pow whose final error is at most 0.5625 ulp agrees
+ * with x * x outside that band. amb_index holds their positions among the kept rows, amb_x / amb_y
+ * their coordinates. A native caller evaluates sqrt(pow(x, 2) + pow(y, 2)) with its C library for
+ * those and writes the results over r with gtf_event_radius_patch; every other r is final. */
+typedef struct gtf_window_in {
+    uint32_t struct_size;        /* sizeof(gtf_window_in) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    int32_t n_rows;              /* rows of the node file (gtf_csv_counts.n_rows) */
+    int32_t pad_;
+    int64_t lo;                  /* min_volume * 1000 */
+    int64_t hi;                  /* (max_volume + 1) * 1000 */
+    const int64_t* node_idx;     /* [n_rows] */
+    const int64_t* layer_id;
+    const double* x;
+    const double* y;
+    const double* z;
+} gtf_window_in;
+
+/* Caller-allocated, each [n_rows] (the bound of both counts); none may be NULL with n_rows > 0. */
+typedef struct gtf_window_out {
+    int64_t* node_idx;
+    int64_t* layer_id;
+    double* x;
+    double* y;
+    double* z;
+    double* r;
+    int32_t* amb_index;
+    double* amb_x;
+    double* amb_y;
+} gtf_window_out;
+
+typedef struct gtf_window_counts {
+    int32_t n_kept;
+    int32_t n_ambiguous;
+} gtf_window_counts;
+
+/* Scratch of gtf_event_window: positive for 0 rows, non-decreasing; about 16 bytes per row. */
+size_t gtf_event_window_workspace_bytes(int32_t n_rows);
+
+/* Two launches around one hipCUB exclusive sum of (kept | ambiguous << 32); no atomics, nothing
+ * allocated. Synchronises `stream` once, to fill *counts. Nothing is written past [n_kept] of the
+ * node columns or [n_ambiguous] of the list. -3 for another ABI of *in; -2 for a null argument or
+ * array, a negative or too large n_rows (> INT32_MAX / 4) or a small workspace, decided on the host
+ * before any launch. n_rows == 0: returns 0 with zero counts, nothing launched. */
+int gtf_event_window(const gtf_window_in* in, const gtf_window_out* out, gtf_window_counts* counts,
+                     void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* r[index[k]] = value[k] for k < n; an index outside [0, n_nodes) writes nothing. One launch, does
+ * not synchronise. -2 for negative sizes or a null array with n > 0. */
+int gtf_event_radius_patch(double* r, int32_t n_nodes, const int32_t* index, const double* value, int32_t n,
+                           gtf_stream_t stream);
 
 /* ---- graph preparation: the optional fields of gtf_graph, built on the GPU -----------
  * The schedules and graph-static slot tables that the lane-group kernels read (every
