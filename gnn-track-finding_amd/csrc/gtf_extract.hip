@@ -580,11 +580,40 @@ __global__ void __launch_bounds__(BLOCK) k_ord_keys(int n, const int32_t* label,
 }
 
 // the sorted ids: range (a negative id is a huge unsigned one) and duplicates
-__global__ void __launch_bounds__(BLOCK) k_ord_check_ids(int n, const uint64_t* ids, int32_t* err) {
+// (evs: the events beside the ids sorted by (event, id), or NULL: equal ids of two events are no duplicate)
+__global__ void __launch_bounds__(BLOCK) k_ord_check_ids(int n, const uint64_t* ids, const uint32_t* evs, int32_t* err) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, OERR_RANGE);      // (only on a violation)
-    if (i > 0 && ids[i] == ids[i - 1]) atomicOr(err, OERR_DUP);
+    if (i > 0 && ids[i] == ids[i - 1] && (!evs || evs[i] == evs[i - 1])) atomicOr(err, OERR_DUP);
+}
+
+// a batch of events: the event of every entry of the id-sorted map, the key of the second (stable) sort
+__global__ void __launch_bounds__(BLOCK) k_ord_ev_keys(int n, const int32_t* event, const int32_t* idx, uint32_t* keys) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int v = idx[i];
+    keys[i] = v >= 0 && v < n ? (uint32_t)event[v] : 0u;
+}
+
+// ... and the ids in the final (event, id) order
+__global__ void __launch_bounds__(BLOCK) k_ord_ev_ids(int n, const int64_t* node_id, const int32_t* idx, uint64_t* ids) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int v = idx[i];
+    ids[i] = v >= 0 && v < n ? (uint64_t)node_id[v] : ~(uint64_t)0;
+}
+
+// find_id (gtf_pyset.h) in a map sorted by (event, id): the node of event `ev` with this id, or -1
+__device__ inline int32_t find_id_ev(const uint32_t* evs, const uint64_t* ids, const int32_t* idx, int32_t n, uint32_t ev,
+                                     int64_t key) {
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t m = (lo + hi) >> 1;
+        if (evs[m] < ev || (evs[m] == ev && ids[m] < (uint64_t)key)) lo = m + 1;
+        else hi = m;
+    }
+    return (lo < n && evs[lo] == ev && ids[lo] == (uint64_t)key) ? idx[lo] : -1;
 }
 
 // is component c (< n_comp) ordered by the set walk? its subgraph has an inactive edge and
@@ -634,6 +663,7 @@ __global__ void __launch_bounds__(BLOCK) k_ord_rank(int n, const int32_t* memb, 
 __global__ void __launch_bounds__(BLOCK) k_ord_walk(gtf_graph g, const uint8_t* act, int n, const int32_t* n_comp,
                                                     const int32_t* cptr, const int32_t* memb,
                                                     const int32_t* so_flag, const int64_t* node_id,
+                                                    const int32_t* event, const uint32_t* evs,
                                                     const uint64_t* ids, const int32_t* idx, const int64_t* toff,
                                                     int64_t* tbl, int64_t tbl_words, int32_t* queue, uint8_t* seen,
                                                     int32_t* order_key, int32_t* err) {
@@ -674,7 +704,8 @@ __global__ void __launch_bounds__(BLOCK) k_ord_walk(gtf_graph g, const uint8_t* 
     int32_t r = 0;
     for (int64_t i = 0; i <= shown.mask; i++) {
         if (shown.a[i] < 0) continue;
-        const int32_t v = find_id(ids, idx, n, shown.a[i]);
+        const int32_t v = event ? find_id_ev(evs, ids, idx, n, (uint32_t)event[root], shown.a[i])
+                                : find_id(ids, idx, n, shown.a[i]);
         if (v >= 0) order_key[v] = r;
         r++;
     }
@@ -713,7 +744,7 @@ OrdWs carve_ord(void* base, int n, int n_sub) {
     w.scal = a.take<int32_t>(16);
     w.seen = a.take<uint8_t>(n);
     w.inactive = a.take<uint8_t>(n_sub > 0 ? n_sub : 1);
-    w.cub = ex_cub_need(n).scan<int64_t>(n + 1).sum<int32_t>(n).max<int32_t>(n).take(a);
+    w.cub = ex_cub_need(n).sort_pairs<uint32_t, int32_t>(n).scan<int64_t>(n + 1).sum<int32_t>(n).max<int32_t>(n).take(a);
     w.tbl_words = 24 * (size_t)n;
     w.tbl = a.take<int64_t>(w.tbl_words);
     w.total = a.used() + 256;
@@ -869,6 +900,15 @@ int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int
                                const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
                                int32_t* order_key, void* workspace, size_t workspace_bytes,
                                gtf_order_counts* counts, gtf_stream_t stream) {
+    return gtf_candidate_order_device_ev(g, e, sub_id, sub_ptr, n_sub, node_id, nullptr, order_key, workspace,
+                                         workspace_bytes, counts, stream);
+}
+
+// (the messages name gtf_candidate_order_device with or without events: one rule, one text)
+int gtf_candidate_order_device_ev(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id,
+                                  const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
+                                  const int32_t* event, int32_t* order_key, void* workspace,
+                                  size_t workspace_bytes, gtf_order_counts* counts, gtf_stream_t stream) {
     const char* who = "gtf_candidate_order_device";
     if (int rc = gtf::check_abi(g, who)) return rc;
     if (!e || !counts || !workspace || g->n_nodes < 0 || g->n_slots < 0 || g->n_edges < 0 || n_sub < 0)
@@ -898,9 +938,22 @@ int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int
     hipLaunchKernelGGL(k_ord_rank, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.memb, w.is_start, w.cidx, w.cptr, sub_id,
                        sub_ptr, w.inactive, order_key);
     // node id -> index (keys_in is free again; vals_in still holds 0 .. n - 1)
-    if ((err = cub.sort_pairs((const uint64_t*)node_id, w.ids, w.vals_in, w.idx, n)) != hipSuccess)
-        return fail(who, "sort ids", err);
-    hipLaunchKernelGGL(k_ord_check_ids, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.ids, w.scal + OS_ERR);
+    uint32_t* evs = nullptr;
+    if (!event) {
+        if ((err = cub.sort_pairs((const uint64_t*)node_id, w.ids, w.vals_in, w.idx, n)) != hipSuccess)
+            return fail(who, "sort ids", err);
+    } else {
+        // by id, then stably by event: the map in (event, id) order. keys_out (its starts are taken) holds the
+        // two arrays of event keys, the walk's queue the map between the sorts.
+        uint32_t* ev_in = (uint32_t*)w.keys_out;
+        evs = ev_in + n;
+        if ((err = cub.sort_pairs((const uint64_t*)node_id, w.keys_in, w.vals_in, w.queue, n)) != hipSuccess)
+            return fail(who, "sort ids", err);
+        hipLaunchKernelGGL(k_ord_ev_keys, dim3(grid(n)), dim3(BLOCK), 0, st, n, event, w.queue, ev_in);
+        if ((err = cub.sort_pairs(ev_in, evs, w.queue, w.idx, n)) != hipSuccess) return fail(who, "sort events", err);
+        hipLaunchKernelGGL(k_ord_ev_ids, dim3(grid(n)), dim3(BLOCK), 0, st, n, node_id, w.idx, w.ids);
+    }
+    hipLaunchKernelGGL(k_ord_check_ids, dim3(grid(n)), dim3(BLOCK), 0, st, n, w.ids, evs, w.scal + OS_ERR);
     // the set-ordered components: table offsets and counts by scans, then one thread each
     hipLaunchKernelGGL(k_ord_words, dim3(grid(n + 1)), dim3(BLOCK), 0, st, n, w.scal + OS_NCOMP, w.cptr, w.memb,
                        sub_id, sub_ptr, w.inactive, w.words, w.so_flag, w.so_size);
@@ -908,7 +961,7 @@ int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int
     if ((err = cub.sum(w.so_flag, w.scal + OS_NSET, n)) != hipSuccess) return fail(who, "sum", err);
     if ((err = cub.max(w.so_size, w.scal + OS_MAXSET, n)) != hipSuccess) return fail(who, "max", err);
     hipLaunchKernelGGL(k_ord_walk, dim3(grid(n)), dim3(BLOCK), 0, st, *g, e->act, n, w.scal + OS_NCOMP, w.cptr, w.memb,
-                       w.so_flag, node_id, w.ids, w.idx, w.toff, w.tbl, (int64_t)w.tbl_words, w.queue, w.seen,
+                       w.so_flag, node_id, event, evs, w.ids, w.idx, w.toff, w.tbl, (int64_t)w.tbl_words, w.queue, w.seen,
                        order_key, w.scal + OS_ERR);
     if ((err = hipGetLastError()) != hipSuccess) return fail(who, "launch", err);
     int32_t scal[4];

@@ -217,6 +217,54 @@ class GtfFillColumn(ctypes.Structure):
 FILL_MAX_COLUMNS = 32   # GTF_FILL_MAX_COLUMNS
 
 
+class GtfConcatSizes(ctypes.Structure):
+    """gtf_concat_sizes: the sizes of one part of gtf_graph_concat (a host array)"""
+    _fields_ = [("n_nodes", I32), ("n_slots", I32), ("n_edges", I32), ("n_sub", I32)]
+
+
+class GtfConcatPart(ctypes.Structure):
+    """gtf_concat_part: one entry of gtf_graph_concat's device table"""
+    _fields_ = [("n_nodes", I32), ("n_slots", I32), ("n_edges", I32), ("n_sub", I32), ("slot_ptr", P),
+                ("slot_src", P), ("out_ptr", P), ("out_slot", P), ("sub_id", P)]
+
+
+class GtfConcatOut(ctypes.Structure):
+    """gtf_concat_out: the structure arrays of the fused graph (NULL = not wanted); keyword construction
+    only -- struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("slot_ptr", P), ("slot_src", P), ("out_ptr", P),
+                ("out_slot", P), ("sub_id", P), ("event", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfConcatOut)
+        self.abi_version = ABI_VERSION
+
+
+class GtfConcatColumn(ctypes.Structure):
+    """gtf_concat_column: one payload column of gtf_concat_columns (src: a device table of n_parts pointers)"""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", I32), ("axis", I32)]
+
+
+CONCAT_MAX_COLUMNS = 32   # GTF_CONCAT_MAX_COLUMNS
+
+
+class GtfSplitIn(ctypes.Structure):
+    """gtf_split_in: the lists of one gtf_extract_outputs call, as node indices; keyword construction
+    only -- struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("cand_ptr", P), ("cand_members", P), ("rem_ptr", P),
+                ("rem_nodes", P), ("frag_ptr", P), ("frag_nodes", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfSplitIn)
+        self.abi_version = ABI_VERSION
+
+
+class GtfSplitOut(ctypes.Structure):
+    """gtf_split_out: gtf_event_split's device outputs"""
+    _fields_ = [("cand_first", P), ("rem_first", P), ("frag_first", P), ("counts", P), ("cand_ptr_ev", P)]
+
+
 CSV_MAX_COLUMNS, CSV_MAX_FIELDS, CSV_MAX_ROW_BYTES = 16, 64, 1024   # GTF_CSV_MAX_*
 CSV_INT64, CSV_DOUBLE = 0, 1                                        # GTF_CSV_INT64 / _DOUBLE
 # GTF_CSV_ERR_*
@@ -333,6 +381,9 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_workspace_bytes",
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
            "gtf_subgraph_ptr_device", "gtf_candidate_order_workspace_bytes", "gtf_candidate_order_device",
+           "gtf_candidate_order_device_ev",
+           "gtf_graph_concat_workspace_bytes", "gtf_graph_concat", "gtf_concat_columns",
+           "gtf_event_split_workspace_bytes", "gtf_event_split",
            "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
            "gtf_score_reset", "gtf_score_workspace_bytes", "gtf_score_candidates",
            "gtf_score_finish_workspace_bytes", "gtf_score_finish",
@@ -414,6 +465,17 @@ def lib(lean: bool = False):
     L.gtf_candidate_order_workspace_bytes.argtypes = [I32, I32, I32]
     L.gtf_candidate_order_device.argtypes = [G, E, P, P, I32, P, P, P, ctypes.c_size_t,
                                              ctypes.POINTER(GtfOrderCounts), P]
+    L.gtf_candidate_order_device_ev.argtypes = [G, E, P, P, I32, P, P, P, P, ctypes.c_size_t,
+                                                ctypes.POINTER(GtfOrderCounts), P]
+    L.gtf_graph_concat_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_graph_concat_workspace_bytes.argtypes = [I32]
+    L.gtf_graph_concat.argtypes = [ctypes.POINTER(GtfConcatSizes), P, I32, ctypes.POINTER(GtfConcatOut), P,
+                                   ctypes.c_size_t, P]
+    L.gtf_concat_columns.argtypes = [P, I32, I32, I32, ctypes.POINTER(GtfConcatColumn), I32, P]
+    L.gtf_event_split_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_event_split_workspace_bytes.argtypes = [I32]
+    L.gtf_event_split.argtypes = [P, I32, I32, ctypes.POINTER(GtfExtractOutCounts), ctypes.POINTER(GtfSplitIn),
+                                  ctypes.POINTER(GtfSplitOut), P, ctypes.c_size_t, P]
     L.gtf_extract_outputs_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_extract_outputs_workspace_bytes.argtypes = [I32, I32]
     L.gtf_extract_outputs.argtypes = [G, ctypes.POINTER(GtfExtractIO), I32, P, ctypes.POINTER(GtfExtractOut), P,
@@ -509,7 +571,8 @@ def lib(lean: bool = False):
                "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_subgraph_ptr_device", "gtf_candidate_order_device",
                "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
                "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
-               "gtf_event_radius_patch"):
+               "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
+               "gtf_event_split"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

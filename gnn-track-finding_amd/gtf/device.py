@@ -982,6 +982,140 @@ class DeviceGraph:
                                       empty_arrays(SLOT_FIELDS, 0), cnt.n_sub), None, True, False)
             c.t["solo"] = solo
         c._finish(shape, False)
+        if hasattr(self, "n_events"):   # (a batch: the child's carried event column names as many events)
+            c.n_events = self.n_events
+        return c
+
+    # ------------------------------------------------ a batch of resident events as one graph
+    @classmethod
+    def concat(cls, parts, mem=None, device=None) -> "DeviceGraph":
+        """gtf.graph.concat on the device (gtf_graph_concat, gtf_concat_columns): the resident graphs
+        `parts` -- natural layout, one allocator and device, as from_event, build_event_dev or subset
+        leave them -- fused into one DeviceGraph with tables == "device" (gtf_graph_prepare), part after
+        part, indices shifted, orphan keys kept. ``carried["event"]`` (int32 [N]) names the part of
+        every node and ``n_events`` their number; the resident node_id column and the parts' carried
+        columns (vivl) are fused with the payload when every part holds them. Parts without nodes are
+        legal anywhere. The number of launches does not depend on len(parts); nothing synchronises
+        (mem "hip": once, before the tables' scratch is freed). host_graph() downloads the result when
+        no part has orphan keys. mem / device: those of the parts (given, they must agree); they decide
+        alone for an empty list."""
+        parts = list(parts)
+        K = len(parts)
+        for d in parts:
+            if not isinstance(d, cls):
+                raise TypeError("DeviceGraph.concat takes DeviceGraphs")
+            if d.layout != "natural" or d.n_pack_waves:
+                raise NotImplementedError("DeviceGraph.concat: only layout='natural' without pack=True (the "
+                                          "renumbered, padded and packed layouts are not carried over); a part has "
+                                          "layout=%r, pack=%r" % (d.layout, bool(d.n_pack_waves)))
+            if not d._sub_ok:
+                raise ValueError("DeviceGraph.concat needs sub_id >= 0 on every node")
+            if d.mem != parts[0].mem or str(d.device) != str(parts[0].device):
+                raise ValueError("DeviceGraph.concat: the parts must share one allocator and device")
+        if parts and mem is not None and mem != parts[0].mem:
+            raise ValueError("DeviceGraph.concat: mem=%r, but the parts were allocated with mem=%r" % (mem, parts[0].mem))
+        mem = parts[0].mem if parts else (mem or "torch")
+        if mem not in ("torch", "hip"):
+            raise ValueError("mem must be 'torch' or 'hip'")
+        c = cls.__new__(cls)
+        c.mem = mem
+        c.torch = torch = _torch() if mem == "torch" else None
+        if parts:
+            c.device, c.lib = parts[0].device, parts[0].lib
+        elif torch is not None:
+            c.device, c.lib = torch.device(device or "cuda"), nat.lib()
+        else:
+            c.device, c.lib = device or "cuda", nat.lib(lean=True)
+            nat.check(c.lib.gtf_device_init(int(c.device.split(":")[1]) if ":" in c.device else 0))
+        c.layout, c.order, c.slot_perm, c.pad_plan = "natural", None, None, None
+        c.slot_ptr_host, c._node_id_host = None, None
+        c.tables = "device"
+        c.t, c.carried = {}, {}
+        c.n_events = K
+        sizes = [(d.n_nodes, d.n_slots, d.n_edges, d.n_sub) for d in parts]
+        N, S, E, B = (sum(z[i] for z in sizes) for i in range(4))
+        if max(N, S, E, B) >= 1 << 31:
+            raise ValueError("DeviceGraph.concat: the parts sum to 2^31 or more nodes, slots, edges or subgraphs")
+        c.n_nodes, c.n_slots, c.n_edges, c.n_sub, c._sub_ok = N, S, E, B, True
+        L, vp = c.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
+        adr = lambda t: t.data_ptr() if t.numel() else 0  # noqa: E731
+        # the columns: (axis, sources, destination, row bytes)
+        cols = []
+
+        def column(axis, name, srcs, dt, width, store):
+            rows = N if axis == 0 else S
+            rb = width * np.dtype(dt).itemsize
+            wb = 8 if rb % 8 == 0 else 4 if rb % 4 == 0 else 1
+            for d, a in zip(parts, srcs):
+                if a.numel() != (d.n_nodes if axis == 0 else d.n_slots) * width:
+                    raise ValueError("DeviceGraph.concat: %r of a part has not one row of %d per %s"
+                                     % (name, width, "node" if axis == 0 else "slot"))
+                if a.numel() and a.data_ptr() % wb:
+                    raise ValueError("DeviceGraph.concat: %r of a part is not aligned to %d bytes" % (name, wb))
+            store[name] = c._dev_empty(rows * width, dt)
+            cols.append((axis, [adr(a) for a in srcs], store[name], rb))
+
+        for f in ("gnn", "xyzr", "layer") + MUTABLE_NODE:
+            dt, shape, _ = NODE_FIELDS[f]
+            column(0, f, [d.t[f] for d in parts], dt, int(np.prod(shape, dtype=np.int64)), c.t)
+        column(0, "solo", [d.t["solo"] for d in parts], np.uint8, 1, c.t)
+        if all("node_id" in d.t or getattr(d, "_node_id_host", None) is not None for d in parts):
+            column(0, "node_id", [d.node_id_dev() for d in parts], np.int64, 1, c.t)
+        names = [set(getattr(d, "carried", {})) for d in parts]
+        for name in sorted(set.intersection(*names) if names else ()):
+            if name == "event":   # (a fused graph as a part: its events become one)
+                continue
+            srcs = [d.carried[name] for d in parts]
+            a0 = srcs[0]
+            dt = a0.dtype if isinstance(a0.dtype, np.dtype) else np.dtype(str(a0.dtype).split(".")[-1])
+            width = next((a.numel() // d.n_nodes for d, a in zip(parts, srcs) if d.n_nodes), 2 if name == "vivl" else 1)
+            column(0, name, srcs, dt, width, c.carried)
+        for f, (dt, shape, _) in SLOT_FIELDS.items():
+            if f not in ("slot_key", "slot_src"):
+                column(1, f, [d.t[f] for d in parts], dt, int(np.prod(shape, dtype=np.int64)), c.t)
+        struct = [("slot_ptr", N + 1), ("slot_src", S), ("out_ptr", N + 1), ("out_slot", E), ("sub_id", N)]
+        for name, n in struct:
+            c.t[name] = c._dev_empty(n, np.int32)
+        c.carried["event"] = c._dev_empty(N, np.int32)
+        # one upload: the part table, then every column's K source pointers
+        ptab = (nat.GtfConcatPart * max(K, 1))(*[
+            nat.GtfConcatPart(d.n_nodes, d.n_slots, d.n_edges, d.n_sub, *[adr(d.t[k]) for k in
+                                                                          ("slot_ptr", "slot_src", "out_ptr", "out_slot",
+                                                                           "sub_id")]) for d in parts])
+        pwords = ctypes.sizeof(nat.GtfConcatPart) // 8
+        host = np.zeros(max(K, 1) * (pwords + len(cols)), np.int64)
+        host[:max(K, 1) * pwords] = np.frombuffer(ptab, np.int64)
+        for i, (_, srcs, _, _) in enumerate(cols):
+            at = max(K, 1) * pwords + i * K
+            host[at:at + K] = srcs
+        tab = c._dev_from(host)
+        nb = int(L.gtf_graph_concat_workspace_bytes(K))
+        ws = c._dev_empty(nb, np.uint8)
+        hs = (nat.GtfConcatSizes * max(K, 1))(*[nat.GtfConcatSizes(*z) for z in sizes])
+        co = nat.GtfConcatOut(event=vp(c.carried["event"]), **{name: c.ptr(name) for name, _ in struct})
+        nat.check(L.gtf_graph_concat(hs, ctypes.c_void_p(tab.data_ptr()), K, ctypes.byref(co), vp(ws),
+                                     ctypes.c_size_t(nb), c.stream))
+        if cols:
+            cc = (nat.GtfConcatColumn * len(cols))(*[
+                nat.GtfConcatColumn(tab.data_ptr() + 8 * (max(K, 1) * pwords + i * K), vp(dst), rb, axis)
+                for i, (axis, _, dst, rb) in enumerate(cols)])
+            nat.check(L.gtf_concat_columns(vp(ws), K, N, S, cc, len(cols), c.stream))
+        # the tables and the workspace go out of scope with kernels in flight: a torch allocation is reused
+        # in stream order, a plain one is freed at once
+        if torch is None:
+            nat.check(L.gtf_stream_synchronize(None))
+        c._event = "node_id" in c.t and "vivl" in c.carried   # (host_graph: the ids and vivl are resident)
+        shape = TrackGraph(N, S, None, None, np.zeros(E, np.int32), {}, {}, B)   # (sizes only)
+        if N > 0 and (S > 0 or E > 0):
+            c._device_tables(shape, None, True)
+        else:   # nothing for gtf_graph_prepare to build: the few tables of a slot-free graph from the host
+            from .graph import empty_arrays
+            zp = np.zeros(N + 1, np.int32)
+            solo = c.t["solo"]
+            c._host_tables(TrackGraph(N, 0, zp, zp, np.zeros(0, np.int32), empty_arrays(NODE_FIELDS, N),
+                                      empty_arrays(SLOT_FIELDS, 0), B), None, True, False)
+            c.t["solo"] = solo
+        c._finish(shape, False)
         return c
 
     # ------------------------------------------------ event conversion into a resident graph

@@ -117,16 +117,24 @@ def candidate_order_dev(d, counts=None):
     """candidate_order() on the device (gtf_candidate_order_device), from the DeviceGraph's own
     arrays: the activation mask a stage just left, sub_id, and the resident node_id column
     (uploaded on first need). Returns the order keys as a device int32 [N] array; counts: an
-    optional dict that receives gtf_order_counts (components, set-ordered ones, the largest)."""
+    optional dict that receives gtf_order_counts (components, set-ordered ones, the largest).
+    A graph that carries an event column (``carried["event"]``: DeviceGraph.concat and its subset()
+    children) goes through gtf_candidate_order_device_ev: node ids distinct within an event."""
     N = d.n_nodes
     sp, nid = sub_ptr_dev(d), d.node_id_dev()
     order = d._dev_empty(max(N, 1), np.int32)
     nb = int(d.lib.gtf_candidate_order_workspace_bytes(N, d.n_slots, d.n_sub))
     ws = d._dev_empty(nb, np.uint8)
     cnt = nat.GtfOrderCounts()
-    nat.check(d.lib.gtf_candidate_order_device(ctypes.byref(d.cg_sched), ctypes.byref(d.ce), d.ptr("sub_id"), _vp(sp),
-                                               d.n_sub, _vp(nid), _vp(order), _vp(ws), ctypes.c_size_t(nb),
-                                               ctypes.byref(cnt), d.stream))
+    ev = getattr(d, "carried", {}).get("event")
+    if ev is not None:   # a batch (DeviceGraph.concat): ids are distinct within an event only
+        nat.check(d.lib.gtf_candidate_order_device_ev(ctypes.byref(d.cg_sched), ctypes.byref(d.ce), d.ptr("sub_id"),
+                                                      _vp(sp), d.n_sub, _vp(nid), _vp(ev), _vp(order), _vp(ws),
+                                                      ctypes.c_size_t(nb), ctypes.byref(cnt), d.stream))
+    else:
+        nat.check(d.lib.gtf_candidate_order_device(ctypes.byref(d.cg_sched), ctypes.byref(d.ce), d.ptr("sub_id"),
+                                                   _vp(sp), d.n_sub, _vp(nid), _vp(order), _vp(ws),
+                                                   ctypes.c_size_t(nb), ctypes.byref(cnt), d.stream))
     if counts is not None:
         counts.update(n_components=cnt.n_components, n_set_ordered=cnt.n_set_ordered,
                       max_set_ordered=cnt.max_set_ordered)
@@ -169,7 +177,7 @@ def _groups(ptr, members):
     return [members[ptr[i]:ptr[i + 1]] for i in range(len(ptr) - 1)]
 
 
-def outputs_dev(d, res, fragment, ids=True, lists=True):
+def outputs_dev(d, res, fragment, ids=True, lists=True, members=False):
     """outputs() on the device (gtf_extract_outputs) from run_dev's result, which must not have
     been reused since. Returns the dict outputs() returns -- the lists as host arrays: of node
     ids (int64) with ids=True, of node indices with ids=False -- plus "keep", the device uint8
@@ -181,18 +189,24 @@ def outputs_dev(d, res, fragment, ids=True, lists=True):
     "rem_nodes", "frag_nodes", int32 indices, with ids=False), "pval_xy", "pval_zr" -- and
     "counts", the six host counts that say how much of each is filled (n_extracted,
     n_extracted_nodes, n_remaining, n_remaining_nodes, n_fragments, n_fragment_nodes): what
-    metrics.DeviceScorer.add and DeviceGraph.subset consume without a host copy."""
+    metrics.DeviceScorer.add and DeviceGraph.subset consume without a host copy.
+    members=True (with ids=True): the index lists "cand_members", "rem_nodes", "frag_nodes" are written
+    beside the id lists -- what split_dev reads a batch's events from."""
     N, n1, S = d.n_nodes, max(d.n_nodes, 1), d.n_sub
+    both = bool(ids and members)
     o = {"left": d._dev_empty(max(S, 1), np.int32), "keep": d._dev_empty(n1, np.uint8),
          "pval_xy": d._dev_empty(n1, np.float64), "pval_zr": d._dev_empty(n1, np.float64)}
     for k in ("cand", "rem", "frag"):
         o[k + "_ptr"] = d._dev_empty(n1 + 1, np.int32)
         o[k + "_list"] = d._dev_empty(n1, np.int64 if ids else np.int32)
+        if both:
+            o[k + "_idx"] = d._dev_empty(n1, np.int32)
     z = ctypes.c_void_p(0)
     lp = [_vp(o[k + "_list"]) for k in ("cand", "rem", "frag")]
-    out = nat.GtfExtractOut(_vp(o["left"]), _vp(o["keep"]), _vp(o["cand_ptr"]), z if ids else lp[0],
-                            _vp(o["pval_xy"]), _vp(o["pval_zr"]), _vp(o["rem_ptr"]), z if ids else lp[1],
-                            _vp(o["frag_ptr"]), z if ids else lp[2], _vp(d.node_id_dev()) if ids else z,
+    ip = [_vp(o[k + "_idx"]) for k in ("cand", "rem", "frag")] if both else ([z, z, z] if ids else lp)
+    out = nat.GtfExtractOut(_vp(o["left"]), _vp(o["keep"]), _vp(o["cand_ptr"]), ip[0],
+                            _vp(o["pval_xy"]), _vp(o["pval_zr"]), _vp(o["rem_ptr"]), ip[1],
+                            _vp(o["frag_ptr"]), ip[2], _vp(d.node_id_dev()) if ids else z,
                             *(lp if ids else (z, z, z)))
     nb = int(d.lib.gtf_extract_outputs_workspace_bytes(N, S))
     ws = d._dev_empty(nb, np.uint8)
@@ -203,6 +217,8 @@ def outputs_dev(d, res, fragment, ids=True, lists=True):
     r = {"keep": o["keep"], "left": o["left"], "pval_xy": o["pval_xy"], "pval_zr": o["pval_zr"]}
     for k in ("cand", "rem", "frag"):
         r[k + "_ptr"], r[_LIST_KEYS[k][0 if ids else 1]] = o[k + "_ptr"], o[k + "_list"]
+        if both:
+            r[_LIST_KEYS[k][1]] = o[k + "_idx"]
     r["counts"] = {f: int(getattr(cnt, f)) for f, _ in nat.GtfExtractOutCounts._fields_}
     return outputs_host(d, r) if lists else r
 
@@ -229,6 +245,36 @@ def outputs_host(d, r):
         h[key] = _groups(host(r[k + "_ptr"], n + 1), host(lst, m)) if d.n_nodes else []
     h["pval_xy"], h["pval_zr"] = host(r["pval_xy"], c["n_extracted"]), host(r["pval_zr"], c["n_extracted"])
     return h
+
+
+def split_dev(d, o, n_events=None):
+    """One extraction's outputs on a fused graph (DeviceGraph.concat, or a subset() child that carries
+    its event column) taken apart per event by gtf_event_split. o: outputs_dev(d, res, fragment,
+    ids=True, lists=False, members=True). Returns {"first": {"cand" | "rem" | "frag": host int32
+    [K + 1], the first group of every event in that list}, "counts": K dicts of the six counts,
+    "cand_ptr_ev": the device array of every event's candidate pointers rebased to 0, event e's at
+    first["cand"][e] + e}. One small download after the call's own synchronisation. Raises
+    RuntimeError (rc -2) when a group spans two events or the events do not ascend."""
+    K = int(getattr(d, "n_events", 0) if n_events is None else n_events)
+    ev = d.carried["event"]
+    c = o["counts"]
+    cnt = nat.GtfExtractOutCounts(*[c[f] for f, _ in nat.GtfExtractOutCounts._fields_])
+    small = d._dev_empty(3 * (K + 1) + 6 * K, np.int32)   # the three first arrays, then the counts
+    pev = d._dev_empty(c["n_extracted"] + K, np.int32)
+    base = small.data_ptr() if small.numel() else 0
+    at = lambda words: ctypes.c_void_p(base + 4 * words if base else 0)  # noqa: E731
+    sin = nat.GtfSplitIn(**{k: _vp(o[k]) for k in ("cand_ptr", "cand_members", "rem_ptr", "rem_nodes", "frag_ptr",
+                                                   "frag_nodes")})
+    sout = nat.GtfSplitOut(at(0), at(K + 1), at(2 * (K + 1)), at(3 * (K + 1)), _vp(pev))
+    nb = int(d.lib.gtf_event_split_workspace_bytes(K))
+    ws = d._dev_empty(nb, np.uint8)
+    nat.check(d.lib.gtf_event_split(_vp(ev), d.n_nodes, K, ctypes.byref(cnt), ctypes.byref(sin), ctypes.byref(sout),
+                                    _vp(ws), ctypes.c_size_t(nb), d.stream))
+    h = d._np(small).astype(np.int32, copy=False) if K else np.zeros(3, np.int32)
+    first = {k: h[i * (K + 1):(i + 1) * (K + 1)] for i, k in enumerate(("cand", "rem", "frag"))}
+    names = [f for f, _ in nat.GtfExtractOutCounts._fields_]
+    counts = [dict(zip(names, (int(x) for x in h[3 * (K + 1) + 6 * e:3 * (K + 1) + 6 * e + 6]))) for e in range(K)]
+    return {"first": first, "counts": counts, "cand_ptr_ev": pev}
 
 
 def candidate_order(g: TrackGraph) -> np.ndarray:

@@ -610,6 +610,37 @@ def concat(graphs: List[TrackGraph]) -> TrackGraph:
     return out
 
 
+def split_events(g: TrackGraph, event, n_events: int) -> List[TrackGraph]:
+    """concat() undone: the fused graph ``g`` cut into its ``n_events`` parts along the node column
+    ``event`` (non-decreasing, values in [0, n_events): the column DeviceGraph.concat writes and
+    subset() carries). Node, slot and out-edge indices lose the part's offsets, an orphan
+    slot_src stays -1, and sub_id is renumbered from the part's first subgraph (the ids are dense
+    and grouped, as pack() and subset() number them). A part without nodes is an empty graph."""
+    event = np.asarray(event, dtype=np.int64).reshape(-1)
+    if event.shape != (g.n_nodes,):
+        raise ValueError("event must name the part of each of the %d nodes" % g.n_nodes)
+    if event.size and (np.any(np.diff(event) < 0) or event[0] < 0 or event[-1] >= n_events):
+        raise ValueError("event must be non-decreasing with values in [0, n_events)")
+    bound = np.searchsorted(event, np.arange(n_events + 1))
+    sp, op = g.slot_ptr.astype(np.int64), g.out_ptr.astype(np.int64)
+    out = []
+    for e in range(n_events):
+        a, b = int(bound[e]), int(bound[e + 1])
+        s0, s1, e0, e1 = int(sp[a]), int(sp[b]), int(op[a]), int(op[b])
+        node = {k: v[a:b].copy() for k, v in g.node.items()}
+        slot = {k: v[s0:s1].copy() for k, v in g.slot.items()}
+        src = slot["slot_src"].astype(np.int64)
+        slot["slot_src"] = np.where(src >= 0, src - a, -1).astype(np.int32)
+        sub = node["sub_id"].astype(np.int64)
+        node["sub_id"] = (sub - (sub[0] if b > a else 0)).astype(np.int32)
+        part = TrackGraph(b - a, s1 - s0, (sp[a:b + 1] - s0).astype(np.int32), (op[a:b + 1] - e0).astype(np.int32),
+                          (g.out_slot[e0:e1].astype(np.int64) - s0).astype(np.int32), node, slot,
+                          int(node["sub_id"].max()) + 1 if b > a else 0)
+        check_layout(part)
+        out.append(part)
+    return out
+
+
 # --------------------------------------------------------------------------
 # subset: the graph a stage saves after removing nodes (extraction)
 # --------------------------------------------------------------------------

@@ -36,7 +36,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import extract
-from .graph import TrackGraph, pack, refresh_send_mw, subset
+from .graph import TrackGraph, concat, pack, refresh_send_mw, split_events, subset
 from .params import Params
 
 CLUSTER_FIRST = (1.0, 2.0)        # run_gnn_trackml_mod.sh:89  -d track_state_estimates -c 1.0 -k 2.0
@@ -169,6 +169,132 @@ def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Para
 
 def _ids(g: TrackGraph, groups):
     return [g.node["node_id"][np.asarray(x, np.int64)] for x in groups]
+
+
+def _dev_slice(d, t, start: int, n: int):
+    """n elements of the device array t from element `start` on (a view, no copy)"""
+    if d.torch is not None:
+        return t[start:start + n]
+    return t.view(start * t.dtype.itemsize, n, t.dtype)
+
+
+def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = None, scorers=None,
+              lists: bool = True, first: int = 1, keep_graphs: bool = False) -> List[List[Iteration]]:
+    """run(d, None, resident="device") for K resident events at once: ``ds`` (the DeviceGraphs of
+    build_event_dev, one allocator and device) are fused by DeviceGraph.concat and the loop runs ONCE on
+    the fused graph, so the synchronisations of an iteration -- the connected-components rounds, the
+    counts read-backs, the subset plan -- are paid per batch instead of per event. Subgraphs of
+    different events share no edge: every stage, the extraction and the node removal compute on the
+    fused graph what they compute on each event, and gtf_event_split (extract.split_dev) takes each
+    iteration's candidates, p-values, remaining and fragment groups and counts apart again. The event
+    column travels through subset() as a carried column. Returns one List[Iteration] per event, equal
+    to run()'s on that event alone: the same records, and as many -- an event's list ends at the first
+    iteration it enters with no node left, as run() breaks. ``seconds`` are the batch's.
+    scorers: None, or one metrics.DeviceScorer (or None) per event; scorers[e] receives event e's
+    candidates of every iteration, group = (first + iterations - 1) - it as in run(). lists=False: no
+    node-id list crosses to the host. The input graphs are not modified.
+    keep_graphs: every record also holds the event's stage output, remaining graph and remaining vivl
+    (what run_pipeline.py saves), cut on the host (graph.split_events) from downloads of the fused
+    graphs after each step -- as in run(), a record's remaining_graph ends holding the next stage's
+    output and merged coordinates.
+    A reference exception (DeviceGraph.raise_errors) in any event raises here as it does in run(); the
+    error word is the fused graph's, so the message does not say which event."""
+    from .device import DeviceGraph
+    p = p or Params()
+    ex = ex or extract.Params()
+    ds = list(ds)
+    K = len(ds)
+    if scorers is not None and len(scorers) != K:
+        raise ValueError("scorers must hold one entry (a DeviceScorer or None) per event")
+    for g in ds:
+        if not isinstance(g, DeviceGraph):
+            raise ValueError("run_batch takes resident events (the DeviceGraphs of build_event_dev)")
+        if "node_id" not in g.t or "vivl" not in getattr(g, "carried", {}):
+            raise ValueError("a DeviceGraph input must hold the node_id and vivl columns (DeviceGraph.from_event)")
+    out = [[] for _ in range(K)]
+    if K == 0:
+        return out
+    t0 = time.perf_counter()
+    d = DeviceGraph.concat(ds)
+    left = [g.n_nodes for g in ds]   # the nodes every event enters the iteration with
+    G = concat([g.host_graph()[0] for g in ds]) if keep_graphs else None   # the fused graph's host copy
+    last = first + iterations - 1
+    for it in range(first, first + iterations):
+        if d.n_nodes == 0:
+            break
+        if it > first:
+            t0 = time.perf_counter()
+        torch = d.torch
+        d.clear_errors()
+        if it == 1:
+            stage = "clustering(track_state_estimates)"
+            d.cluster("tse", CLUSTER_FIRST[0], CLUSTER_FIRST[1], p)
+        elif it % 2 == 0:
+            stage = "extrapolation"
+            d.extrapolate(p)
+        else:
+            stage = "clustering(updated_track_states)"
+            d.cluster("uts", CLUSTER_LATER[0], CLUSTER_LATER[1], p)
+        d.raise_errors()
+        if torch is not None:
+            torch.cuda.synchronize(d.device)
+        t1 = time.perf_counter()
+        vivl_dev, event_dev = d.carried["vivl"], d.carried["event"]
+        order = extract.candidate_order_dev(d)
+        res = extract.run_dev(d, vivl_dev, ex, order)
+        t2 = time.perf_counter()
+        o = extract.outputs_dev(d, res, ex.numhits, ids=True, lists=False, members=True)
+        sp = extract.split_dev(d, o, K)
+        fc, fr, ff = (sp["first"][k] for k in ("cand", "rem", "frag"))
+        if scorers is not None:
+            at = 0   # event e's members start where the events before it end
+            for e in range(K):
+                ce = sp["counts"][e]
+                if scorers[e] is not None and left[e] > 0:
+                    scorers[e].add(_dev_slice(d, sp["cand_ptr_ev"], int(fc[e]) + e, ce["n_extracted"] + 1),
+                                   _dev_slice(d, o["cand_ids"], at, ce["n_extracted_nodes"]), ce["n_extracted"],
+                                   last - it, n_members=ce["n_extracted_nodes"])
+                at += ce["n_extracted_nodes"]
+        n_ext = o["counts"]["n_extracted"]
+        if lists:
+            h = extract.outputs_host(d, o)
+        else:   # (the p-values are per candidate, not lists of node ids: they come back)
+            h = {k: d._np(_dev_slice(d, o[k], 0, n_ext)) if n_ext else np.empty(0, np.float64)
+                 for k in ("pval_xy", "pval_zr")}
+        dnext = d.subset(o["keep"], gnn=res["gnn"], carry={"vivl": vivl_dev, "event": event_dev})
+        dnext.refresh_send_mw()
+        if it % 2 == 0 and dnext.n_nodes:      # remove_state_metadata.py, as in run()
+            dnext.clear_errors()
+            dnext.update(p)
+            dnext.raise_errors()
+        t3 = time.perf_counter()
+        seconds = {"stage": t1 - t0, "extract": t2 - t1, "next": t3 - t2}
+        if keep_graphs:   # after the step (it left d's arrays as the stage wrote them), as in run()
+            ev = d._np(event_dev)
+            nets = split_events(d.download(G), ev, K)
+            G.node["gnn"] = d._np(res["gnn"]).reshape(-1, 4)
+            for e, part in enumerate(split_events(G, ev, K)):   # the iteration's input graphs, as run() leaves them
+                if out[e] and left[e] > 0:
+                    out[e][-1].remaining_graph = part
+            G = dnext.to_host(G)
+            ev2 = d._np(dnext.carried["event"])
+            rems, vivl2 = split_events(G, ev2, K), d._np(dnext.carried["vivl"]).reshape(-1, 2)
+            cut = np.searchsorted(ev2, np.arange(K + 1))
+        for e in range(K):
+            if left[e] == 0:
+                continue
+            c0, c1 = int(fc[e]), int(fc[e + 1])
+            grp = (lambda key, a, b: h[key][a:b]) if lists else (lambda key, a, b: None)
+            out[e].append(Iteration(it, stage, grp("extracted", c0, c1), h["pval_xy"][c0:c1], h["pval_zr"][c0:c1],
+                                    grp("remaining", int(fr[e]), int(fr[e + 1])),
+                                    grp("fragments", int(ff[e]), int(ff[e + 1])), dict(seconds),
+                                    counts=dict(sp["counts"][e])))
+            if keep_graphs:
+                rec = out[e][-1]
+                rec.network, rec.remaining_graph, rec.remaining_vivl = nets[e], rems[e], vivl2[cut[e]:cut[e + 1]]
+            left[e] = sp["counts"][e]["n_remaining_nodes"]
+        d = dnext
+    return out
 
 
 def run(g, vivl, iterations: int = 3, p: Params = None, ex: extract.Params = None,

@@ -29,6 +29,13 @@ pipeline.build_event_dev(parse="device")) and, with --resident-truth, the truth 
 (gtf.metrics.truth_files_dev). One line per file says which parser read it: a file with a field outside
 the device parser's exact domain is read by the host reader. The same files either way.
 
+--batch DIR [DIR ...] takes several --eventNetwork directories at once: every event is built in GPU memory
+(as --resident-event), the events are fused (DeviceGraph.concat) and the loop runs once on the fused graph
+(pipeline.run_batch); with --truth (one directory for every event, or one per event) the candidates are
+scored on the GPU as with --resident-metrics. Event i's files go under ROOTDIR/<i>/ in the layout above, the
+same files a single run of that event writes. If a stage raises a reference exception the whole batch
+stops; the message does not say which event.
+
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
 """
@@ -72,11 +79,11 @@ def _parser_line(key, info):
     print("parse %s: %s%s" % (key, info[key], " (%s)" % info[key + "_reason"] if key + "_reason" in info else ""))
 
 
-def _scorers(args):
+def _scorers(args, truth_dir=None):
     """the truth files as reconstruction_efficiency.score reads them -> the two device scorers"""
     import numpy as np
     from gtf import metrics
-    pre = os.path.join(args.truth, "event000001000-")
+    pre = os.path.join(truth_dir or args.truth, "event000001000-")
     if args.resident_parse and args.resident_truth:
         tables, info = metrics.truth_files_dev(pre, args.mapping, args.min_volume, args.max_volume, args.device)
         for key in ("particles", "mapping", "truth"):
@@ -134,11 +141,25 @@ def main(argv=None):
     ap.add_argument("--resident-parse", action="store_true",
                     help="as --resident-event, and the CSV files are parsed on the GPU (gtf_csv_parse); with "
                          "--resident-truth the truth files as well; only with --start 1")
-    ap.add_argument("--truth", help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py)")
+    ap.add_argument("--batch", nargs="+", metavar="DIR",
+                    help="several event_network directories: the events are built in GPU memory, fused and run as one "
+                         "loop (pipeline.run_batch); event i's outputs go under ROOTDIR/<i>/; only with --start 1")
+    ap.add_argument("--truth", nargs="+", metavar="DIR",
+                    help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py); with --batch one "
+                         "directory for every event, or one per event")
     ap.add_argument("--mapping", default="full-mapping-minCurv-0.3-800.csv", help="mapping file under --truth")
     args = ap.parse_args(argv)
     if args.start < 1 or args.end < args.start:
         ap.error("need 1 <= start <= end")
+    args.truth_dirs = args.truth or []
+    if args.truth_dirs and len(args.truth_dirs) != 1 and (not args.batch or len(args.truth_dirs) != len(args.batch)):
+        ap.error("--truth takes one directory (with --batch: one, or one per event)")
+    args.truth = args.truth_dirs[0] if args.truth_dirs else None
+    if args.batch:
+        if args.start != 1:
+            ap.error("--batch converts the events: only with --start 1")
+        if args.eventNetwork:
+            ap.error("--batch names the event directories itself: not with -n")
     if args.resident_parse:
         args.resident_event = True
     if args.resident_event and args.start != 1:
@@ -151,6 +172,8 @@ def main(argv=None):
                endcap_boundary=args.endcapboundary, chi2_cut=args.chi2)
     ex = extract.Params(args.pval, args.numhits, args.separation, args.merge, args.sigma0xy, args.sigma0rz,
                         args.endcapboundary)
+    if args.batch:
+        return _batch(args, p, ex)
     root = args.outputDir
     times = {}
     if args.start == 1:
@@ -184,6 +207,13 @@ def main(argv=None):
         on_dev = args.resident_outputs or args.resident_event or args.resident_metrics
         its = pipeline.run(g, vivl, args.end - args.start + 1, p, ex, args.device, first=args.start, keep_graphs=True,
                            resident="device" if on_dev else args.resident, **extra)
+    _save(root, its, times)
+    _metrics(args, root, its, scorers, args.truth)
+    return 0
+
+
+def _save(root, its, times):
+    """the iterations' files and timings.json under root"""
     for it in its:
         d = os.path.join(root, "iteration_%d" % it.index)
         store.save_graph(os.path.join(_dir(d, "network"), "graph.npz"), it.network)
@@ -201,7 +231,11 @@ def main(argv=None):
               % (it.index, it.stage, len(it.candidates), len(it.remaining), len(it.fragments)))
     with open(os.path.join(_dir(root), "timings.json"), "w") as f:
         json.dump(times, f, indent=1)
-    if args.truth and its:
+
+
+def _metrics(args, root, its, scorers, truth_dir):
+    """metrics.json under root: from the device scorers, else from the saved lists"""
+    if truth_dir and its:
         from extract import reconstruction_efficiency as re_cli
         from gtf import metrics
         res = {}
@@ -209,12 +243,41 @@ def main(argv=None):
             if scorers:
                 r = (scorers.cumulative if cum else scorers.last).result()
             else:
-                r = re_cli.score(args.truth, root, args.min_volume, args.max_volume, its[-1].index, args.mapping, cum)
+                r = re_cli.score(truth_dir, root, args.min_volume, args.max_volume, its[-1].index, args.mapping, cum)
             res[name] = metrics.summary(r)
             print("%s: %d / %d reference tracks reconstructed, efficiency %s %%"
                   % (name, r.n_reconstructed, r.n_reference, r.efficiency_str))
         with open(os.path.join(root, "metrics.json"), "w") as f:
             json.dump(res, f, indent=1)
+
+
+def _batch(args, p, ex):
+    """--batch: the events built in GPU memory, one fused loop, event i's files under ROOTDIR/<i>/"""
+    devs, times = [], []
+    for i, dn in enumerate(args.batch):
+        t0 = time.perf_counter()
+        dev = pipeline.build_event_dev(os.path.join(dn, "event_1_filtered_graph_"), args.min_volume, args.max_volume, p,
+                                       args.device, parse="device" if args.resident_parse else "host")
+        if args.resident_parse:
+            for key in ("nodes", "edges"):
+                _parser_line(key, dev.parse_info)
+        g, vivl = dev.host_graph()
+        times.append({"event_conversion": time.perf_counter() - t0})
+        store.save_graph(os.path.join(_dir(args.outputDir, str(i), "track_sim", "network"), "graph.npz"), g, vivl)
+        print("event %d conversion: %d nodes, %d directed edges, %d subgraphs (%.3f s)"
+              % (i, g.n_nodes, g.n_edges, g.n_subgraphs, times[i]["event_conversion"]))
+        devs.append(dev)
+    truth = [None] * len(devs)
+    if args.truth_dirs:
+        truth = args.truth_dirs if len(args.truth_dirs) > 1 else args.truth_dirs * len(devs)
+    scorers = [_scorers(args, t) if t else None for t in truth]
+    its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=scorers if args.truth_dirs else None,
+                             first=1, keep_graphs=True)
+    for i, rec in enumerate(its):
+        root = os.path.join(args.outputDir, str(i))
+        print("event %d:" % i)
+        _save(root, rec, times[i])
+        _metrics(args, root, rec, scorers[i], truth[i])
     return 0
 
 

@@ -39,6 +39,9 @@
  *                       (utilities/helper.py:524-543, reconstruction_efficiency.py:41-47)
  *   gtf_event_window, gtf_event_radius_patch
  *                    -> utilities/helper.py:526-531 (the volume window) and :12-13 (r)
+ *   gtf_graph_concat, gtf_concat_columns, gtf_candidate_order_device_ev, gtf_event_split
+ *                    -> no reference counterpart: a batch of events as one graph, in place of
+ *                       running run_gnn_trackml_mod.sh once per event
  */
 #ifndef GTF_H
 #define GTF_H
@@ -633,6 +636,17 @@ int gtf_candidate_order_device(const gtf_graph* g, const gtf_edges* e, const int
                                const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
                                int32_t* order_key, void* workspace, size_t workspace_bytes,
                                gtf_order_counts* counts, gtf_stream_t stream);
+/* The same on a batch of events (gtf_graph_concat): `event` [N] (device) names the event of
+ * every node, and node ids must be distinct within an event only -- the ids of different
+ * events collide, and they cannot be shifted apart because the set order of a small component
+ * hashes the id itself. The id -> node map is sorted by (event, id) instead of id (two stable
+ * radix sorts) and a set-ordered component looks its ids up among its own event's. Any int32
+ * values, in any node order. event == NULL: gtf_candidate_order_device, which is this call
+ * with NULL. Same workspace size, same statuses and messages. */
+int gtf_candidate_order_device_ev(const gtf_graph* g, const gtf_edges* e, const int32_t* sub_id,
+                                  const int32_t* sub_ptr, int32_t n_sub, const int64_t* node_id,
+                                  const int32_t* event, int32_t* order_key, void* workspace,
+                                  size_t workspace_bytes, gtf_order_counts* counts, gtf_stream_t stream);
 
 /* gtf_extract_outputs: the stage's outputs (extract_track_candidates.py:423-430 the remaining
  * and fragment subgraphs, :459-467 the node removal; gtf/extract.py outputs) from the results
@@ -1408,6 +1422,132 @@ int gtf_subset_gather(const void* workspace, int32_t axis, const gtf_column* col
  * binary search in u's segment. send_mw may not alias tse_mw. Does not synchronise. */
 int gtf_refresh_send_mw(const gtf_graph* g, const int32_t* tse_rank, const double* tse_mw, double* send_mw,
                         gtf_stream_t stream);
+
+/* ---- a batch of resident events: gtf_graph_concat / gtf_event_split ---------------------
+ * gtf/graph.py concat on the device: K resident graphs in natural layout (what
+ * gtf_build_event_csr_device + gtf_event_pack, or gtf_graph_subset_apply, leave) become one
+ * graph whose nodes, slots, out-edges and subgraphs are the parts', part after part, with the
+ * indices shifted by the sizes of the parts before. Subgraphs of different parts share no
+ * edge, so every stage of run_gnn_trackml_mod.sh computes on the fused graph what it computes
+ * on each part, and gtf_event_split takes one extraction's outputs apart again. The
+ * schedules and slot tables of the fused graph come from gtf_graph_prepare. gtf_concat.hip.
+ *
+ * The number of launches does not depend on K: one launch for the offsets, one for the
+ * structure arrays, one per 32 payload columns. Nothing synchronises, nothing is allocated. */
+
+/* The sizes of one part: a HOST array [n_parts] (the sums are checked before any launch). */
+typedef struct gtf_concat_sizes {
+    int32_t n_nodes, n_slots, n_edges, n_sub;
+} gtf_concat_sizes;
+
+/* One part: an entry of a DEVICE (or host-mapped) array [n_parts]. The sizes repeat the host
+ * array's; an array of a part without rows of that kind may be NULL. */
+typedef struct gtf_concat_part {
+    int32_t n_nodes, n_slots, n_edges, n_sub;
+    const int32_t* slot_ptr;   /* [n_nodes+1] */
+    const int32_t* slot_src;   /* [n_slots]   -1 = orphan key, kept */
+    const int32_t* out_ptr;    /* [n_nodes+1] */
+    const int32_t* out_slot;   /* [n_edges] */
+    const int32_t* sub_id;     /* [n_nodes]   values in [0, n_sub) */
+} gtf_concat_part;
+
+/* The structure arrays of the fused graph, DEVICE arrays at the summed sizes N, S, E;
+ * NULL = not wanted. */
+typedef struct gtf_concat_out {
+    uint32_t struct_size;   /* sizeof(gtf_concat_out) as the caller compiled it */
+    uint32_t abi_version;   /* GTF_ABI_VERSION */
+    int32_t* slot_ptr;   /* [N+1] */
+    int32_t* slot_src;   /* [S] */
+    int32_t* out_ptr;    /* [N+1] */
+    int32_t* out_slot;   /* [E] */
+    int32_t* sub_id;     /* [N] part's sub_id + the subgraphs of the parts before */
+    int32_t* event;      /* [N] the part index of every node */
+} gtf_concat_out;
+
+#define GTF_CONCAT_MAX_COLUMNS 32
+
+/* One payload column of gtf_concat_columns: dst row (offset of part p + i) = row i of src[p].
+ * Rows that are multiples of 8 bytes move as 8-byte words, of 4 as 4-byte words, others as
+ * bytes; dst and every src[p] that has rows must be aligned to that word. */
+typedef struct gtf_concat_column {
+    const void* const* src;   /* DEVICE array [n_parts] of device pointers; an entry of a part without rows is not read */
+    void* dst;                /* device: [sum of rows] of row_bytes each */
+    int32_t row_bytes;        /* >= 1 */
+    int32_t axis;             /* 0 = one row per node, 1 = per slot */
+} gtf_concat_column;
+
+/* positive for 0 parts, non-decreasing (a negative count as 0) */
+size_t gtf_graph_concat_workspace_bytes(int32_t n_parts);
+
+/* Offsets and structure arrays (gtf/graph.py concat). `sizes` is read on the host, `parts` on
+ * the device; the kernels clamp every write to the host sums, so a device table that
+ * disagrees with `sizes` writes nothing outside the outputs. Leaves the four offset arrays
+ * in `workspace`, which gtf_concat_columns reads: it stays the caller's until `stream` has
+ * run those calls. Parts without nodes are legal anywhere. n_parts == 0 or no node at all:
+ * slot_ptr[0] = out_ptr[0] = 0 is all that is written.
+ * -3: *out built against another layout of this header (struct_size, abi_version).
+ * -2, decided on the host before any launch: a NULL sizes, parts, out or workspace, a
+ * negative n_parts or size, slots or edges in a part without nodes, a sum of nodes, slots,
+ * edges or subgraphs of 2^31 or more, a workspace below gtf_graph_concat_workspace_bytes. */
+int gtf_graph_concat(const gtf_concat_sizes* sizes, const gtf_concat_part* parts, int32_t n_parts,
+                     const gtf_concat_out* out, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* The payload (the np.concatenate of every field in gtf/graph.py concat) after gtf_graph_concat
+ * on the same workspace and stream: `cols` is a HOST array of any length, 32 columns travel in
+ * the kernel arguments of one launch; only the per-part source pointers lie in device memory.
+ * n_nodes / n_slots: the summed sizes given to gtf_graph_concat (the rows of dst per axis).
+ * -2: a NULL workspace or column table, negative sizes, row_bytes < 1, an axis that is not
+ * 0 / 1, a NULL or misaligned dst, a NULL src table, a column of 2^63 bytes or more. */
+int gtf_concat_columns(const void* workspace, int32_t n_parts, int32_t n_nodes, int32_t n_slots,
+                       const gtf_concat_column* cols, int32_t n_cols, gtf_stream_t stream);
+
+/* gtf_event_split: the lists of ONE gtf_extract_outputs call on a fused graph, per event.
+ * Candidate ids are the smallest node index of their component and candidates ascend by id;
+ * the remaining and the fragment groups are in subgraph order; concat and subset keep the node
+ * order. So the groups of an event are one run of each list, and the events' runs follow each
+ * other in event order: the first group of event e is the lower bound of e among the events
+ * of the groups' first members.
+ * `in`: the pointer and node-index arrays as gtf_extract_out holds them, with the six host
+ * counts of that call; `event` [n_nodes] the fused graph's event column, values in
+ * [0, n_events). `out`, DEVICE arrays:
+ *   cand_first, rem_first, frag_first [n_events + 1]  the first group of every event (the
+ *                                                     last entry: the number of groups)
+ *   counts [n_events][6]     gtf_extract_out_counts of every event, in the struct's order
+ *   cand_ptr_ev [n_extracted + n_events]  every event's candidate pointers rebased to 0, event
+ *                            e's n_e + 1 entries at cand_first[e] + e: with the members from
+ *                            in->cand_ptr[cand_first[e]] on, gtf_score_candidates' input
+ * The kernels check what the rule relies on: a group without members, a member outside
+ * [0, n_nodes), an event outside [0, n_events), members of one group in two events, first
+ * members whose events decrease, pointers that decrease or leave the counts. Any of them
+ * sets an error word (the only atomic) and the call returns -2 after its one synchronisation;
+ * the outputs then hold nothing to rely on, but every write stayed inside them.
+ * -3: *in built against another layout of this header (struct_size, abi_version).
+ * Also -2, on the host before any launch: a NULL argument or array of a non-empty list,
+ * negative sizes, a workspace below gtf_event_split_workspace_bytes. n_events == 0: returns
+ * 0, nothing launched. */
+typedef struct gtf_split_in {
+    uint32_t struct_size;         /* sizeof(gtf_split_in) as the caller compiled it */
+    uint32_t abi_version;         /* GTF_ABI_VERSION */
+    const int32_t* cand_ptr;      /* [n_extracted + 1] */
+    const int32_t* cand_members;  /* [n_extracted_nodes] node indices */
+    const int32_t* rem_ptr;       /* [n_remaining + 1] */
+    const int32_t* rem_nodes;     /* [n_remaining_nodes] */
+    const int32_t* frag_ptr;      /* [n_fragments + 1] */
+    const int32_t* frag_nodes;    /* [n_fragment_nodes] */
+} gtf_split_in;
+
+typedef struct gtf_split_out {
+    int32_t* cand_first;
+    int32_t* rem_first;
+    int32_t* frag_first;
+    int32_t* counts;
+    int32_t* cand_ptr_ev;
+} gtf_split_out;
+
+size_t gtf_event_split_workspace_bytes(int32_t n_events);
+int gtf_event_split(const int32_t* event, int32_t n_nodes, int32_t n_events,
+                    const gtf_extract_out_counts* counts, const gtf_split_in* in, const gtf_split_out* out,
+                    void* workspace, size_t workspace_bytes, gtf_stream_t stream);
 
 /* Member order of every extraction candidate as the reference builds it: CCA over the
  * active edges of each subgraph (extract_track_candidates.py:332-346) -- networkx
