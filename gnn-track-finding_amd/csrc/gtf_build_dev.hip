@@ -27,6 +27,14 @@
 //
 // Integer and byte work only: sorts and scans are hipCUB, the rest one thread per row /
 // edge / node / component. Not on the timed path (once per event).
+//
+// A batch of events (gtf_build_events_csr_device) is the same build on the events' columns
+// laid end to end: a graph whose components never cross an event boundary. Its sorts, scans,
+// hook rounds, slot keys and out-lists run on global indices as they are and leave the arrays
+// gtf/graph.py concat defines; three steps know the event of what they handle and have a
+// batch form beside the single-event kernel (the *_ev kernels below): the id -> CSV index
+// map, sorted by (event, id) and searched inside the event's segment; the 2|c| >= |G| rule,
+// with |G| the node count of the component's own event; and the event column.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -37,7 +45,6 @@
 
 namespace {
 
-using gtf::bad;
 using gtf::fail;
 using gtf::grid;
 
@@ -275,13 +282,183 @@ __global__ void k_tse_rank(const int32_t* order, int64_t n, const int32_t* slot_
     }
 }
 
+// ---- the batch forms: `off` [K + 1] are the events' offsets on the node or the row axis ----
+
+// the event whose range [off[e], off[e + 1]) holds i < off[K] (events without rows share an
+// offset: the last of them that starts at or before i is the one that holds it)
+__device__ inline int32_t event_of(const int32_t* off, int32_t K, int32_t i) {
+    int32_t lo = 0, hi = K - 1;
+    while (lo < hi) {
+        const int32_t m = (lo + hi) >> 1;
+        if (off[m + 1] <= i) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+
+// the ids come sorted by id with the CSV index each came from: the event of every entry, the
+// key of the stable sort that makes it (event, id) order
+__global__ void k_event_keys(const int32_t* idx, int64_t n, const int32_t* noff, int32_t K, uint64_t* key) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) key[i] = (uint64_t)event_of(noff, K, idx[i]);
+}
+
+__global__ void k_gather_ids(const int64_t* node_id, const int32_t* idx, int64_t n, uint64_t* ids) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) ids[i] = (uint64_t)node_id[idx[i]];
+}
+
+// ids in (event, id) order: event e's are positions [noff[e], noff[e + 1]). A repeated id is
+// an error inside one event only; err[3] keeps the first such event.
+__global__ void k_check_ids_ev(const uint64_t* ids, int64_t n, const int32_t* noff, int32_t K, int32_t* err) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, ERR_RANGE);
+    if (i > 0 && ids[i] == ids[i - 1]) {
+        const int32_t e = event_of(noff, K, (int32_t)i);
+        if (i > noff[e]) {
+            atomicOr(err, ERR_DUP);
+            atomicMin(err + 3, e);
+        }
+    }
+}
+
+// k_rows with both ends looked up among the nodes of the row's own event
+__global__ void k_rows_ev(const int64_t* ra, const int64_t* rb, int64_t R, const uint64_t* ids, const int32_t* idx,
+                          const int32_t* noff, const int32_t* roff, int32_t K, uint64_t* key, int32_t* t) {
+    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= R) return;
+    const int32_t e = event_of(roff, K, (int32_t)r), lo = noff[e], hi = noff[e + 1];
+    const int32_t ia = find_id_in(ids, idx, lo, hi, ra[r]), ib = find_id_in(ids, idx, lo, hi, rb[r]);
+    const bool ok = ia >= 0 && ib >= 0;
+    key[2 * r] = ok ? ((uint64_t)ia << 32) | (uint32_t)ib : NONE;
+    key[2 * r + 1] = ok ? ((uint64_t)ib << 32) | (uint32_t)ia : NONE;
+    t[2 * r] = (int32_t)(2 * r);
+    t[2 * r + 1] = (int32_t)(2 * r + 1);
+}
+
+// true when component c (its members from memb[lo] on, `sz` of them) gets CSV order: at least
+// half of its own event's nodes
+__device__ inline bool csv_order_ev(const int32_t* noff, int32_t K, int32_t member, int32_t sz) {
+    const int32_t e = event_of(noff, K, member);
+    return 2 * (int64_t)sz >= (int64_t)(noff[e + 1] - noff[e]);
+}
+
+// CSV-index order everywhere (k_comp_order_ev then overwrites the components under half of
+// their event), so `order` is a permutation whatever comes after
+__global__ void k_order_sorted_ev(const int32_t* memb, int64_t n, int32_t* order) {
+    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p < n) order[p] = memb[p];
+}
+
+__global__ void k_comp_words_ev(const int32_t* size, const int32_t* coff, const int32_t* memb, int32_t n_sub,
+                                const int32_t* noff, int32_t K, int64_t* words) {
+    const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c > n_sub) return;
+    words[c] = (c < n_sub && !csv_order_ev(noff, K, memb[coff[c]], size[c])) ? 3 * set_capacity(size[c]) : 0;
+}
+
+// k_comp_order for the components under half of their own event; the set's ids go back to
+// CSV indices inside that event's segment of the map
+__global__ void k_comp_order_ev(const int32_t* memb, const int32_t* coff, const int32_t* size, int32_t n_sub,
+                                const int32_t* noff, int32_t K, const int32_t* gptr, const int32_t* gdst,
+                                const int64_t* node_id, const uint64_t* ids, const int32_t* idx, const int64_t* toff,
+                                int64_t* tbl, int32_t* queue, uint8_t* seen, int32_t* order, int32_t* err) {
+    const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= n_sub) return;
+    const int32_t lo = coff[c], sz = size[c], root = memb[lo];
+    if (csv_order_ev(noff, K, root, sz)) return;
+    const int32_t e = event_of(noff, K, root);
+    const int64_t cap = set_capacity(sz);
+    int64_t* t = tbl + toff[c];
+    DevSet s;
+    s.init(t, t + cap, cap);
+    int32_t head = lo, tail = lo;
+    seen[root] = 1;
+    s.add(node_id[root]);
+    queue[tail++] = root;
+    while (head < tail) {
+        const int32_t v = queue[head++];
+        for (int32_t j = gptr[v]; j < gptr[v + 1]; j++) {
+            const int32_t w = gdst[j];
+            if (!seen[w] && tail < lo + sz) {
+                seen[w] = 1;
+                s.add(node_id[w]);
+                queue[tail++] = w;
+            }
+        }
+    }
+    DevSet shown;
+    int64_t* spare = (s.a == t) ? t + cap : t;   // the first set's spare table
+    shown.init(spare, t + 2 * cap, cap);
+    for (int64_t i = 0; i <= s.mask; i++)
+        if (s.a[i] >= 0) shown.add(s.a[i]);
+    if (s.over || shown.over) { atomicOr(err, ERR_OVER); return; }
+    int32_t r = lo;
+    for (int64_t i = 0; i <= shown.mask; i++) {
+        if (shown.a[i] < 0) continue;
+        const int32_t g = find_id_in(ids, idx, noff[e], noff[e + 1], shown.a[i]);
+        if (g >= 0 && r < lo + sz) order[r++] = g;
+    }
+}
+
+// k_out_slot with the write clamped to the `cap` entries of out_slot
+__global__ void k_out_slot_ev(const uint64_t* gkey, const int32_t* gdst, const int32_t* gptr, int32_t m,
+                              const int32_t* pos, const int32_t* slot_ptr, const int32_t* slot_src,
+                              const int32_t* out_ptr, int32_t* out_slot, int64_t cap) {
+    const int32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const int32_t u = (int32_t)(gkey[i] >> 33), p = pos[u], q = pos[gdst[i]];
+    const int64_t at = (int64_t)out_ptr[p] + (i - gptr[u]);
+    if (at >= 0 && at < cap) out_slot[at] = lower(slot_src, slot_ptr[q], slot_ptr[q + 1], p);
+}
+
+// k_tse_rank with the keys looked up inside the node's own event
+__global__ void k_tse_rank_ev(const int32_t* order, int64_t n, const int32_t* noff, int32_t K, const int32_t* slot_ptr,
+                              const int32_t* slot_src, const int32_t* gptr, const int32_t* gdst, const int32_t* pos,
+                              const int64_t* node_id, const uint64_t* ids, const int32_t* idx, const int64_t* toff,
+                              int64_t* tbl, int32_t* tse_rank, int64_t cap_out, int32_t* err) {
+    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const int32_t b = slot_ptr[p], e = slot_ptr[p + 1], u = order[p];
+    if (b < 0 || e < b || e > cap_out) { atomicOr(err, ERR_ASYM); return; }
+    const int32_t ev = event_of(noff, K, u), lo = noff[ev], hi = noff[ev + 1];
+    const int64_t cap = set_capacity(e - b);
+    DevSet s;
+    s.init(tbl + toff[p], tbl + toff[p] + cap, cap);
+    for (int32_t k = b; k < e; k++) {
+        s.add(node_id[order[slot_src[k]]]);
+        tse_rank[k] = -1;
+    }
+    for (int32_t j = gptr[u]; j < gptr[u + 1]; j++) s.add(node_id[gdst[j]]);
+    if (s.over) { atomicOr(err, ERR_OVER); return; }
+    int32_t r = 0;
+    for (int64_t i = s.mask; i >= 0; i--) {   // reversed iteration order
+        if (s.a[i] < 0) continue;
+        const int32_t g = find_id_in(ids, idx, lo, hi, s.a[i]);
+        if (g < 0) { atomicOr(err, ERR_ASYM); return; }
+        const int32_t q = pos[g];
+        const int32_t f = lower(slot_src, b, e, q);
+        if (f == e || slot_src[f] != q) { atomicOr(err, ERR_ASYM); return; }
+        tse_rank[f] = r++;
+    }
+}
+
+// components are ranked by their minimum global CSV index, so event e's packed nodes are the
+// positions [noff[e], noff[e + 1]): the event column is a function of the position
+__global__ void k_event_column(const int32_t* noff, int32_t K, int64_t n, int32_t* event) {
+    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p < n) event[p] = event_of(noff, K, (int32_t)p);
+}
+
 struct BuildWs {
     uint64_t *ids, *ka, *kb, *gk;
     int32_t *idx, *iota, *va, *vb, *gv;
     int32_t *gdeg, *gptr, *lab, *isroot, *rank, *comp, *size, *coff, *memb, *pos, *queue, *rdeg, *od;
     uint8_t* seen;
     int64_t *words, *toff, *tbl;
-    int32_t* scal;   // [0] error bits, [1] changed, [2] valid edges
+    int32_t* scal;   // [0] error bits, [1] changed, [2] valid edges, [3] a batch's first event with a repeated id
+    int32_t *noff, *roff;   // a batch: the events' node and row offsets, [K + 1] each
     gtf::Scratch cub;
     size_t tbl_words, total;
 };
@@ -289,7 +466,8 @@ struct BuildWs {
 // capacity bound: a set of k distinct keys has a table of <= 8 max(k, 1) entries, so the
 // component tables (3 per component) take <= 24 N words and the key-order tables (2 per
 // node) <= 16 (S + N)
-BuildWs carve(void* base, int64_t N, int64_t R) {
+// K: the events of a batch, whose two offset tables follow the single event's layout (-1: none)
+BuildWs carve(void* base, int64_t N, int64_t R, int64_t K = -1) {
     const int64_t E2 = 2 * R, M = N > E2 ? N : E2;
     const size_t n = (size_t)N, n1 = n + 1, m = (size_t)M, e2 = (size_t)(E2 > 0 ? E2 : 1);
     gtf::Arena a(base);
@@ -327,41 +505,43 @@ BuildWs carve(void* base, int64_t N, int64_t R) {
     const int64_t t1 = 24 * (N > 0 ? N : 1), t2 = 16 * (E2 + N + 1);
     w.tbl_words = (size_t)(t1 > t2 ? t1 : t2);
     w.tbl = a.take<int64_t>(w.tbl_words);
+    w.noff = w.roff = nullptr;
+    if (K >= 0) {
+        w.noff = a.take<int32_t>((size_t)K + 1);
+        w.roff = a.take<int32_t>((size_t)K + 1);
+    }
     w.total = a.used() + 256;
     return w;
 }
 
-size_t carve_bytes(int64_t N, int64_t R) { return carve(nullptr, N, R).total; }
+size_t carve_bytes(int64_t N, int64_t R, int64_t K = -1) { return carve(nullptr, N, R, K).total; }
 
-}  // namespace
-
-extern "C" {
-
-size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows) {
-    return carve_bytes(n_nodes > 0 ? n_nodes : 0, n_rows > 0 ? n_rows : 0);
+// "who: what" as the error text, `rc` as the status
+int say(int rc, const char* who, const char* what) {
+    char m[256];
+    snprintf(m, sizeof(m), "%s: %s", who, what);
+    gtf::set_error(m);
+    return rc;
 }
 
-int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
-    if (!ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
-        (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
-        (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot)) || !workspace)
-        return bad("gtf_build_event_csr_device: bad arguments");
-    const char* who = "gtf_build_event_csr_device";
+bool bad_event_args(const gtf_event_csr* ev, const void* workspace) {
+    return !ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
+           (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
+           (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot)) || !workspace;
+}
+
+// The build behind both entry points, their arguments checked. K == 0: one event, the
+// single-event kernels. K > 0: a batch of K events whose offsets noff / roff (host arrays)
+// go into the workspace first; the steps that know the event launch their *_ev form, every
+// other launch, sort, scan and synchronisation is the single event's.
+int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* roff, int32_t* event, const char* who,
+              const BuildWs& w, hipStream_t st) {
     const int64_t N = ev->n_nodes, R = ev->n_rows, E2 = 2 * R;
-    if (N > INT32_MAX / 2 || E2 > INT32_MAX / 2)
-        return bad("gtf_build_event_csr_device: graph too large for int32 indices");
-    if (workspace_bytes < carve_bytes(N, R))
-        return bad("gtf_build_event_csr_device: workspace smaller than gtf_build_event_device_workspace_bytes");
-    hipStream_t st = (hipStream_t)stream;
-    const BuildWs w = carve(workspace, N, R);
     const gtf::Cub cub{w.cub, st};
     // a failure that is not a HIP call's: -1 with its own text
-    auto broken = [](const char* what) {
-        gtf::set_error(what);
-        return -1;
-    };
+    auto broken = [who](const char* what) { return say(-1, who, what); };
     hipError_t e;
-    const int32_t zero4[3] = {0, 0, 0};
+    const int32_t zero4[4] = {0, 0, 0, INT32_MAX};
     if ((e = hipMemcpyAsync(w.scal, zero4, sizeof(zero4), hipMemcpyHostToDevice, st)) != hipSuccess)
         return fail(who, "scalars", e);
     if (N == 0) {
@@ -375,25 +555,52 @@ int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t worksp
     const int64_t M2 = N > E2 ? N : E2;
     // 1. ids -> CSV index
     hipLaunchKernelGGL(k_iota, dim3(grid(M2)), dim3(BLOCK), 0, st, w.iota, M2);
-    if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.ids, w.iota, w.idx, (int)N)) != hipSuccess)
-        return fail(who, "sort ids", e);
-    hipLaunchKernelGGL(k_check_ids, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.scal);
+    if (K == 0) {
+        if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.ids, w.iota, w.idx, (int)N)) != hipSuccess)
+            return fail(who, "sort ids", e);
+        hipLaunchKernelGGL(k_check_ids, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.scal);
+    } else {
+        // ids of different events collide and cannot be shifted apart (both set orders hash the id
+        // itself): the id sort, then a stable sort by the event over the bits K needs, leaves event
+        // e's ids ascending at [noff[e], noff[e + 1])
+        if ((e = hipMemcpyAsync(w.noff, noff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(w.roff, roff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(who, "offsets", e);
+        int bits = 1;
+        while (bits < 32 && ((int64_t)1 << bits) < K) bits++;
+        if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.kb, w.iota, w.va, (int)N)) != hipSuccess)
+            return fail(who, "sort ids", e);
+        hipLaunchKernelGGL(k_event_keys, dim3(grid(N)), dim3(BLOCK), 0, st, w.va, N, w.noff, K, w.ka);
+        if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.idx, (int)N, bits)) != hipSuccess) return fail(who, "sort events", e);
+        hipLaunchKernelGGL(k_gather_ids, dim3(grid(N)), dim3(BLOCK), 0, st, ev->node_id, w.idx, N, w.ids);
+        hipLaunchKernelGGL(k_check_ids_ev, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.noff, K, w.scal);
+        if (event) hipLaunchKernelGGL(k_event_column, dim3(grid(N)), dim3(BLOCK), 0, st, w.noff, K, N, event);
+    }
     // 2. G's successor lists in insertion order
     int32_t m = 0;
     if (R > 0) {
-        hipLaunchKernelGGL(k_rows, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx, (int32_t)N,
-                           w.ka, w.va);
+        if (K == 0)
+            hipLaunchKernelGGL(k_rows, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx,
+                               (int32_t)N, w.ka, w.va);
+        else
+            hipLaunchKernelGGL(k_rows_ev, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx,
+                               w.noff, w.roff, K, w.ka, w.va);
         if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.vb, (int)E2)) != hipSuccess) return fail(who, "sort pairs", e);
         hipLaunchKernelGGL(k_first, dim3(grid(E2)), dim3(BLOCK), 0, st, w.kb, w.vb, E2, w.ka, w.va);
         if ((e = cub.sort_pairs(w.ka, w.gk, w.va, w.gv, (int)E2)) != hipSuccess) return fail(who, "sort succ", e);
         hipLaunchKernelGGL(k_count_valid, dim3(grid(E2)), dim3(BLOCK), 0, st, w.gk, E2, w.scal + 2);
     }
-    int32_t scal[3];
+    int32_t scal[4];
     if ((e = hipMemcpyAsync(scal, w.scal, sizeof(scal), hipMemcpyDeviceToHost, st)) != hipSuccess)
         return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
-    if (scal[0] & ERR_RANGE) return bad("gtf_build_event_csr_device: node ids must be in [0, 2^61 - 1)");
-    if (scal[0] & ERR_DUP) return bad("gtf_build_event_csr_device: duplicate node id");
+    if (scal[0] & ERR_RANGE) return say(-2, who, "node ids must be in [0, 2^61 - 1)");
+    if (scal[0] & ERR_DUP) {
+        if (K == 0) return say(-2, who, "duplicate node id");
+        char what[64];
+        snprintf(what, sizeof(what), "duplicate node id in event %d", scal[3]);
+        return say(-2, who, what);
+    }
     m = scal[2];
     const uint64_t* gkey = w.gk;   // kept edges by (u, insertion time); value: v
     const int32_t* gdst = w.gv;
@@ -403,7 +610,7 @@ int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t worksp
     // 3. weakly connected components, labelled by their minimum CSV index
     hipLaunchKernelGGL(k_lab_init, dim3(grid(N)), dim3(BLOCK), 0, st, w.lab, N);
     for (int round = 0; m > 0; round++) {
-        if (round > 200) return broken("gtf_build_event_csr_device: components did not converge");
+        if (round > 200) return broken("components did not converge");
         int32_t z = 0, changed = 0;
         if ((e = hipMemcpyAsync(w.scal + 1, &z, 4, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(who, "flag", e);
         hipLaunchKernelGGL(k_hook, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, m, w.lab, w.scal + 1);
@@ -424,17 +631,28 @@ int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t worksp
     // 4. node order of every component's copy: CSV-index order (the stable sort by
     // component), replaced by the set order for components under half the graph
     if ((e = cub.sort_pairs(w.ka, w.kb, w.iota, w.memb, (int)N, 32)) != hipSuccess) return fail(who, "sort members", e);
-    hipLaunchKernelGGL(k_order_sorted, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, w.comp, w.size, N, ev->order);
-    hipLaunchKernelGGL(k_comp_words, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, n_sub, N, w.words);
+    if (K == 0) {
+        hipLaunchKernelGGL(k_order_sorted, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, w.comp, w.size, N, ev->order);
+        hipLaunchKernelGGL(k_comp_words, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, n_sub, N, w.words);
+    } else {   // |G| of the 2|c| >= |G| rule: the node count of the component's own event
+        hipLaunchKernelGGL(k_order_sorted_ev, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, N, ev->order);
+        hipLaunchKernelGGL(k_comp_words_ev, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, w.coff, w.memb, n_sub,
+                           w.noff, K, w.words);
+    }
     if ((e = cub.scan(w.words, w.toff, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     int64_t words = 0;
     if ((e = hipMemcpyAsync(&words, w.toff + n_sub, 8, hipMemcpyDeviceToHost, st)) != hipSuccess)
         return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
-    if ((size_t)words > w.tbl_words) return broken("gtf_build_event_csr_device: set tables exceed the workspace bound");
+    if ((size_t)words > w.tbl_words) return broken("set tables exceed the workspace bound");
     if ((e = hipMemsetAsync(w.seen, 0, N, st)) != hipSuccess) return fail(who, "memset", e);
-    hipLaunchKernelGGL(k_comp_order, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub, N, w.gptr,
-                       gkey, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen, ev->order, w.scal);
+    if (K == 0)
+        hipLaunchKernelGGL(k_comp_order, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub, N, w.gptr,
+                           gkey, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen, ev->order, w.scal);
+    else
+        hipLaunchKernelGGL(k_comp_order_ev, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub,
+                           w.noff, K, w.gptr, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen,
+                           ev->order, w.scal);
     hipLaunchKernelGGL(k_pos, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, w.comp, N, w.pos, ev->sub_id);
     // 5. slots: (packed receiver, packed sender) in order; the out-lists; the key orders
     if ((e = hipMemsetAsync(w.rdeg, 0, 4 * (N + 1), st)) != hipSuccess) return fail(who, "memset", e);
@@ -446,24 +664,75 @@ int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t worksp
     if ((e = cub.scan(w.rdeg, ev->slot_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     hipLaunchKernelGGL(k_outdeg, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->order, w.gdeg, N, w.od);
     if ((e = cub.scan(w.od, ev->out_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
-    if (m > 0)
+    if (m > 0 && K == 0)
         hipLaunchKernelGGL(k_out_slot, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, w.gptr, m, w.pos, ev->slot_ptr,
                            ev->slot_src, ev->out_ptr, ev->out_slot);
+    else if (m > 0)
+        hipLaunchKernelGGL(k_out_slot_ev, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, w.gptr, m, w.pos,
+                           ev->slot_ptr, ev->slot_src, ev->out_ptr, ev->out_slot, E2);
     hipLaunchKernelGGL(k_tse_words, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->slot_ptr, N, w.words);
     if ((e = cub.scan(w.words, w.toff, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     if ((e = hipMemcpyAsync(&words, w.toff + N, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
-    if ((size_t)words > w.tbl_words) return broken("gtf_build_event_csr_device: set tables exceed the workspace bound");
-    hipLaunchKernelGGL(k_tse_rank, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, ev->slot_ptr, ev->slot_src, w.gptr,
-                       gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank, w.scal);
+    if ((size_t)words > w.tbl_words) return broken("set tables exceed the workspace bound");
+    if (K == 0)
+        hipLaunchKernelGGL(k_tse_rank, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, ev->slot_ptr, ev->slot_src,
+                           w.gptr, gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank, w.scal);
+    else
+        hipLaunchKernelGGL(k_tse_rank_ev, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, w.noff, K, ev->slot_ptr,
+                           ev->slot_src, w.gptr, gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank,
+                           E2, w.scal);
     if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
     if ((e = hipMemcpyAsync(scal, w.scal, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
-    if (scal[0] & ERR_OVER) return broken("gtf_build_event_csr_device: a set held more keys than its table was sized for");
-    if (scal[0] & ERR_ASYM) return broken("gtf_build_event_csr_device: neighbour without an in-edge (graph not symmetric)");
+    if (scal[0] & ERR_OVER) return broken("a set held more keys than its table was sized for");
+    if (scal[0] & ERR_ASYM) return broken("neighbour without an in-edge (graph not symmetric)");
     ev->n_edges = m;
     ev->n_subgraphs = n_sub;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows) {
+    return carve_bytes(n_nodes > 0 ? n_nodes : 0, n_rows > 0 ? n_rows : 0);
+}
+
+int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
+    const char* who = "gtf_build_event_csr_device";
+    if (bad_event_args(ev, workspace)) return say(-2, who, "bad arguments");
+    const int64_t N = ev->n_nodes, R = ev->n_rows;
+    if (N > INT32_MAX / 2 || 2 * R > INT32_MAX / 2) return say(-2, who, "graph too large for int32 indices");
+    if (workspace_bytes < carve_bytes(N, R))
+        return say(-2, who, "workspace smaller than gtf_build_event_device_workspace_bytes");
+    return build_csr(ev, 0, nullptr, nullptr, nullptr, who, carve(workspace, N, R), (hipStream_t)stream);
+}
+
+size_t gtf_build_events_device_workspace_bytes(int64_t n_nodes, int64_t n_rows, int32_t n_events) {
+    return carve_bytes(n_nodes > 0 ? n_nodes : 0, n_rows > 0 ? n_rows : 0, n_events > 0 ? n_events : 0);
+}
+
+int gtf_build_events_csr_device(gtf_event_csr* ev, const gtf_event_batch* b, void* workspace, size_t workspace_bytes,
+                                gtf_stream_t stream) {
+    const char* who = "gtf_build_events_csr_device";
+    if (const int rc = gtf::check_abi(b, who, "gtf_event_batch", "batch")) return rc;
+    if (bad_event_args(ev, workspace) || b->n_events < 0 || !b->node_off || !b->row_off)
+        return say(-2, who, "bad arguments");
+    const int64_t N = ev->n_nodes, R = ev->n_rows;
+    const int32_t K = b->n_events;
+    if (N > INT32_MAX / 2 || 2 * R > INT32_MAX / 2) return say(-2, who, "batch too large for int32 indices");
+    for (const int32_t* off : {b->node_off, b->row_off}) {
+        if (off[0] != 0) return say(-2, who, "node_off and row_off start at 0");
+        for (int32_t e = 0; e < K; e++)
+            if (off[e + 1] < off[e]) return say(-2, who, "node_off and row_off may not decrease");
+    }
+    if (b->node_off[K] != N || b->row_off[K] != R)
+        return say(-2, who, "node_off and row_off end at n_nodes and n_rows");
+    if (workspace_bytes < carve_bytes(N, R, K))
+        return say(-2, who, "workspace smaller than gtf_build_events_device_workspace_bytes");
+    return build_csr(ev, K, b->node_off, b->row_off, b->event, who, carve(workspace, N, R, K), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -106,6 +106,18 @@ __device__ inline int32_t find_id(const uint64_t* ids, const int32_t* idx, int32
     return (lo < n && ids[lo] == (uint64_t)key) ? idx[lo] : -1;
 }
 
+// find_id inside the segment [lo, hi) of a map sorted by (event, id): the index of `key`
+// among one event's nodes, -1 if that event does not hold it (another one may)
+__device__ inline int32_t find_id_in(const uint64_t* ids, const int32_t* idx, int32_t lo, int32_t hi, int64_t key) {
+    const int32_t end = hi;
+    while (lo < hi) {
+        const int32_t m = (lo + hi) >> 1;
+        if (ids[m] < (uint64_t)key) lo = m + 1;
+        else hi = m;
+    }
+    return (lo < end && ids[lo] == (uint64_t)key) ? idx[lo] : -1;
+}
+
 }  // namespace
 
 #endif

@@ -198,6 +198,19 @@ class GtfEventCsr(ctypes.Structure):
                 ("out_ptr", P), ("out_slot", P), ("n_edges", ctypes.c_int64), ("n_subgraphs", I32), ("pad_", I32)]
 
 
+class GtfEventBatch(ctypes.Structure):
+    """gtf_event_batch: the events of gtf_build_events_csr_device (node_off / row_off: HOST int32 [K + 1];
+    event: a device int32 [N] or NULL); keyword construction only -- struct_size / abi_version are filled in
+    (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_events", I32), ("pad_", I32), ("node_off", P),
+                ("row_off", P), ("event", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfEventBatch)
+        self.abi_version = ABI_VERSION
+
+
 class GtfEventCols(ctypes.Structure):
     """gtf_event_cols: the CSV columns of the kept nodes, device arrays in CSV row order"""
     _fields_ = [("x", P), ("y", P), ("z", P), ("r", P), ("layer_id", P)]
@@ -389,6 +402,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_score_finish_workspace_bytes", "gtf_score_finish",
            "gtf_truth_build_workspace_bytes", "gtf_truth_build",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
+           "gtf_build_events_device_workspace_bytes", "gtf_build_events_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
            "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_event_pack", "gtf_fill_columns",
@@ -510,6 +524,10 @@ def lib(lean: bool = False):
     L.gtf_build_event_device_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_build_event_device_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     L.gtf_build_event_csr_device.argtypes = [ctypes.POINTER(GtfEventCsr), P, ctypes.c_size_t, P]
+    L.gtf_build_events_device_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_build_events_device_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, I32]
+    L.gtf_build_events_csr_device.argtypes = [ctypes.POINTER(GtfEventCsr), ctypes.POINTER(GtfEventBatch), P,
+                                              ctypes.c_size_t, P]
     L.gtf_graph_prepare_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_graph_prepare_workspace_bytes.argtypes = [I32, I32, I32]
     L.gtf_graph_prepare.argtypes = [G, ctypes.POINTER(GtfGraphTables), P, ctypes.c_size_t, P]
@@ -572,7 +590,7 @@ def lib(lean: bool = False):
                "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
                "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
-               "gtf_event_split"):
+               "gtf_event_split", "gtf_build_events_csr_device"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

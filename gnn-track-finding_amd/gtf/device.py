@@ -1135,9 +1135,119 @@ class DeviceGraph:
         return cls._from_event(ids, x, y, z, r, layer_id, row_a, row_b, device, mem, lambda part: None)
 
     @classmethod
-    def _from_event(cls, ids, x, y, z, r, layer_id, row_a, row_b, device, mem, mark):
+    def _event_shell(cls, device, mem):
+        """an empty DeviceGraph of from_event's kind: the allocator, the library, natural layout"""
+        if mem not in ("torch", "hip"):
+            raise ValueError("mem must be 'torch' or 'hip'")
+        c = cls.__new__(cls)
+        c.mem = mem
+        c.torch = torch = _torch() if mem == "torch" else None
+        if torch is not None:
+            c.device = torch.device(device)
+            c.lib = nat.lib()
+        else:
+            c.device = device
+            c.lib = nat.lib(lean=True)
+            nat.check(c.lib.gtf_device_init(int(device.split(":")[1]) if ":" in device else 0))
+        c.layout, c.order, c.slot_perm, c.pad_plan = "natural", None, None, None
+        c.slot_ptr_host, c._node_id_host = None, None
+        c.tables = "device"
+        c.t, c.carried = {}, {}
+        c._event = True   # (host_graph: a whole event, its ids resident -- not a subset() child)
+        return c
+
+    @classmethod
+    def from_events(cls, parts, device: str = "cuda", mem: str = "torch"):
+        """DeviceGraph.concat([from_event(*p) for p in parts]) in ONE build: ``parts`` is a list of
+        from_event's eight columns (ids, x, y, z, r, layer_id, row_a, row_b), all host or all device
+        arrays. Host columns are concatenated and go up once per column; device columns are gathered by
+        gtf_graph_concat's offsets and gtf_concat_columns (the node and the row axis; no launch per
+        part). Then, each once on the batch: gtf_build_events_csr_device, gtf_event_pack,
+        gtf_fill_columns and gtf_graph_prepare. The same arrays, carried columns (vivl, event) and
+        sizes as the concat, bit for bit; ``n_events`` = len(parts) and ``event_nodes`` the host list of
+        the events' node counts (known from the inputs, nothing is read back). Node ids belong to their
+        event: the same event twice is legal. Events without nodes or without rows are legal anywhere;
+        the synchronisations do not grow with len(parts)."""
+        return cls._from_events(parts, device, mem, lambda part: None)
+
+    @classmethod
+    def _from_events(cls, parts, device, mem, mark):
+        """from_events; mark as _from_event's (tools/batch_build.py)"""
+        parts = [tuple(p) for p in parts]
+        if any(len(p) != 8 for p in parts):
+            raise ValueError("from_events: every part holds from_event's eight columns")
+        K = len(parts)
+        on_dev = [hasattr(a, "data_ptr") for p in parts for a in p]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("from_events: the columns are all host arrays or all device arrays")
+        c = cls._event_shell(device, mem)
+        INT, FLT = (0, 5, 6, 7), (1, 2, 3, 4)   # (ids, layer_id, row_a, row_b: int64; x, y, z, r: float64)
+        if K and on_dev[0]:
+            size = lambda a: int(a.numel())  # noqa: E731
+        else:
+            parts = [tuple(np.ascontiguousarray(a, np.int64 if i in INT else np.float64).reshape(-1)
+                           for i, a in enumerate(p)) for p in parts]
+            size = lambda a: int(a.size)  # noqa: E731
+        for p in parts:
+            if any(size(p[i]) != size(p[0]) for i in (1, 2, 3, 4, 5)) or size(p[6]) != size(p[7]):
+                raise ValueError("from_events: one x, y, z, r and layer_id per node id, one row_b per row_a")
+        # (the rows of an event without nodes name no node of it: every one would be dropped)
+        nn = [size(p[0]) for p in parts]
+        nr = [size(p[6]) if size(p[0]) else 0 for p in parts]
+        node_off = np.concatenate([[0], np.cumsum(nn, dtype=np.int64)]).astype(np.int64)
+        row_off = np.concatenate([[0], np.cumsum(nr, dtype=np.int64)]).astype(np.int64)
+        N, R = int(node_off[-1]), int(row_off[-1])
+        if max(N, 2 * R) > (2 ** 31 - 1) // 2:
+            raise ValueError("from_events: the batch is too large for int32 indices")
+        if K and on_dev[0]:
+            cols = cls._gather_columns(c, parts, nn, nr, N, R) if N else [c._dev_empty(0, np.int64)] * 8
+        else:
+            cols = [np.concatenate([p[i][:(nr[e] if i > 5 else nn[e])] for e, p in enumerate(parts)])
+                    if K else np.zeros(0, np.int64 if i in INT else np.float64) for i in range(8)]
+        d = cls._from_event(*cols, device, mem, mark, shell=c,
+                            batch=(node_off.astype(np.int32), row_off.astype(np.int32)))
+        d.n_events, d.event_nodes = K, nn
+        return d
+
+    @staticmethod
+    def _gather_columns(c, parts, nn, nr, N, R):
+        """the eight device columns of every part end to end: gtf_graph_concat with no structure output
+        (its offsets: the nodes, and the rows on the slot axis) and gtf_concat_columns"""
+        K = len(parts)
+        L, vp = c.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
+        adr = lambda t: t.data_ptr() if t.numel() else 0  # noqa: E731
+        for p in parts:
+            if any(adr(a) % 8 for a in p):
+                raise ValueError("from_events: a device column is not aligned to 8 bytes")
+        dst = [c._dev_empty(R if i > 5 else N, np.int64 if i in (0, 5, 6, 7) else np.float64) for i in range(8)]
+        ptab = (nat.GtfConcatPart * K)(*[nat.GtfConcatPart(nn[e], nr[e], 0, 0, 0, 0, 0, 0, 0) for e in range(K)])
+        pwords = ctypes.sizeof(nat.GtfConcatPart) // 8
+        host = np.zeros(K * (pwords + 8), np.int64)
+        host[:K * pwords] = np.frombuffer(ptab, np.int64)
+        for i in range(8):
+            host[K * (pwords + i):K * (pwords + i + 1)] = [adr(p[i]) if (nr[e] if i > 5 else nn[e]) else 0
+                                                           for e, p in enumerate(parts)]
+        tab = c._dev_from(host)
+        nb = int(L.gtf_graph_concat_workspace_bytes(K))
+        ws = c._dev_empty(nb, np.uint8)
+        hs = (nat.GtfConcatSizes * K)(*[nat.GtfConcatSizes(nn[e], nr[e], 0, 0) for e in range(K)])
+        nat.check(L.gtf_graph_concat(hs, ctypes.c_void_p(tab.data_ptr()), K, ctypes.byref(nat.GtfConcatOut()),
+                                     vp(ws), ctypes.c_size_t(nb), c.stream))
+        cc = (nat.GtfConcatColumn * 8)(*[nat.GtfConcatColumn(tab.data_ptr() + 8 * K * (pwords + i), vp(dst[i]), 8,
+                                                             1 if i > 5 else 0) for i in range(8)])
+        nat.check(L.gtf_concat_columns(vp(ws), K, N, R, cc, 8, c.stream))
+        # the tables and the workspace go out of scope with kernels in flight: a torch allocation is reused
+        # in stream order, a plain one is freed at once
+        if c.torch is None:
+            nat.check(L.gtf_stream_synchronize(None))
+        return dst
+
+    @classmethod
+    def _from_event(cls, ids, x, y, z, r, layer_id, row_a, row_b, device, mem, mark, shell=None, batch=None):
         """from_event; mark is called with "upload", "csr", "pack_fill" and "prepare" as each part has
-        been issued (tools/resident_event.py synchronises and reads the clock there)"""
+        been issued (tools/resident_event.py synchronises and reads the clock there). batch: the
+        (node_off, row_off) of from_events, whose columns these are -- the CSR is then
+        gtf_build_events_csr_device's and carried["event"] its event column; shell: its _event_shell."""
         if mem not in ("torch", "hip"):
             raise ValueError("mem must be 'torch' or 'hip'")
         on_dev = hasattr(ids, "data_ptr")   # device columns (gtf.io.read_nodes_dev / read_edges_dev)
@@ -1157,23 +1267,12 @@ class DeviceGraph:
                 raise ValueError("from_event: one x, y, z, r and layer_id per node id, one row_b per row_a")
             if N and int(layer_id.min()) < 0:
                 raise ValueError("from_event: negative layer_id")
-        c = cls.__new__(cls)
-        c.mem = mem
-        c.torch = torch = _torch() if mem == "torch" else None
-        if torch is not None:
-            c.device = torch.device(device)
-            c.lib = nat.lib()
-        else:
-            c.device = device
-            c.lib = nat.lib(lean=True)
-            nat.check(c.lib.gtf_device_init(int(device.split(":")[1]) if ":" in device else 0))
-        c.layout, c.order, c.slot_perm, c.pad_plan = "natural", None, None, None
-        c.slot_ptr_host, c._node_id_host = None, None
-        c.tables = "device"
-        c.t, c.carried = {}, {}
-        c._event = True   # (host_graph: a whole event, its ids resident -- not a subset() child)
+        c = shell if shell is not None else cls._event_shell(device, mem)
+        torch = c.torch
         L, vp = c.lib, (lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else 0))
         E = n_sub = 0
+        if batch is not None:
+            c.carried["event"] = c._dev_empty(N, np.int32)
         if N:
             up = {k: a if on_dev else c._dev_from(a) for k, a in (("ids", ids), ("a", row_a), ("b", row_b), ("x", x),
                                                                   ("y", y), ("z", z), ("r", r), ("layer_id", layer_id))}
@@ -1181,12 +1280,21 @@ class DeviceGraph:
             csr = {k: c._dev_empty(n, np.int32) for k, n in (("order", N), ("sub_id", N), ("slot_ptr", N + 1),
                                                               ("slot_src", 2 * R), ("tse_rank", 2 * R),
                                                               ("out_ptr", N + 1), ("out_slot", 2 * R))}
-            nb = int(L.gtf_build_event_device_workspace_bytes(N, R))
-            ws = c._dev_empty(nb, np.uint8)
             ev = nat.GtfEventCsr(N, R, vp(up["ids"]), vp(up["a"]), vp(up["b"]),
                                  *[vp(csr[k]) for k in ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank",
                                                         "out_ptr", "out_slot")], 0, 0, 0)
-            nat.check(L.gtf_build_event_csr_device(ctypes.byref(ev), vp(ws), ctypes.c_size_t(nb), c.stream))
+            if batch is None:
+                nb = int(L.gtf_build_event_device_workspace_bytes(N, R))
+                ws = c._dev_empty(nb, np.uint8)
+                nat.check(L.gtf_build_event_csr_device(ctypes.byref(ev), vp(ws), ctypes.c_size_t(nb), c.stream))
+            else:
+                node_off, row_off = batch
+                nb = int(L.gtf_build_events_device_workspace_bytes(N, R, node_off.size - 1))
+                ws = c._dev_empty(nb, np.uint8)
+                bt = nat.GtfEventBatch(n_events=node_off.size - 1, node_off=node_off.ctypes.data,
+                                       row_off=row_off.ctypes.data, event=vp(c.carried["event"]))
+                nat.check(L.gtf_build_events_csr_device(ctypes.byref(ev), ctypes.byref(bt), vp(ws),
+                                                        ctypes.c_size_t(nb), c.stream))
             E, n_sub = int(ev.n_edges), int(ev.n_subgraphs)
             for k in ("sub_id", "slot_ptr", "out_ptr"):
                 c.t[k] = csr[k]

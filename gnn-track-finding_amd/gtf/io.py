@@ -307,6 +307,78 @@ def csr_from_rows(ids, a, b, device=None):
     return {k: v.cpu().numpy() for k, v in o.items()}, int(ev.n_edges), int(ev.n_subgraphs)
 
 
+BATCH_CSR = ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank", "out_ptr", "out_slot")
+
+
+def csr_from_rows_batch(parts, device=None):
+    """The packed CSR of a batch of events, ``parts`` a list of (ids, a, b) as csr_from_rows takes
+    them: every event's own build, shifted by the sizes of the events before it as gtf.graph.concat
+    shifts -- order and slot_src by the nodes, sub_id by the subgraphs, slot_ptr and out_slot by
+    the slots, out_ptr by the edges, tse_rank as it is -- plus ``event`` [N], the event of every
+    packed node. device=None: that definition, csr_from_rows on the host once per event. With a
+    device: gtf_build_events_csr_device, ONE build on the concatenated columns, the same arrays bit
+    for bit. Node ids belong to their event: the same id may appear in several events, and a row
+    names nodes of its own event only. An event's error names it ("... in event e").
+    Returns (arrays at their exact sizes [N], [N + 1], [E], n_edges, n_subgraphs)."""
+    import ctypes
+    from . import _native as nat
+    parts = [tuple(np.ascontiguousarray(c, np.int64).reshape(-1) for c in part) for part in parts]
+    for ids, a, b in parts:
+        if a.size != b.size:
+            raise ValueError("csr_from_rows_batch: one b per a")
+    K = len(parts)
+    node_off = np.zeros(K + 1, np.int64)
+    row_off = np.zeros(K + 1, np.int64)
+    np.cumsum([p[0].size for p in parts], out=node_off[1:])
+    np.cumsum([p[1].size for p in parts], out=row_off[1:])
+    N, R = int(node_off[-1]), int(row_off[-1])
+    if device is None:
+        cols = {k: [] for k in BATCH_CSR + ("event",)}
+        S = B = 0   # slots (= edges) and subgraphs of the events before
+        for e, (ids, a, b) in enumerate(parts):
+            try:
+                o, E, n_sub = csr_from_rows(ids, a, b)
+            except RuntimeError as err:
+                raise RuntimeError("%s in event %d" % (err, e)) from None
+            n = int(ids.size)
+            cols["order"].append(o["order"][:n] + np.int32(node_off[e]))
+            cols["sub_id"].append(o["sub_id"][:n] + np.int32(B))
+            cols["slot_ptr"].append(o["slot_ptr"][:n] + np.int32(S))
+            cols["out_ptr"].append(o["out_ptr"][:n] + np.int32(S))
+            cols["slot_src"].append(o["slot_src"][:E] + np.int32(node_off[e]))
+            cols["out_slot"].append(o["out_slot"][:E] + np.int32(S))
+            cols["tse_rank"].append(o["tse_rank"][:E])
+            cols["event"].append(np.full(n, e, np.int32))
+            S, B = S + E, B + n_sub
+        for k in ("slot_ptr", "out_ptr"):
+            cols[k].append(np.array([S], np.int32))
+        return {k: np.concatenate(v).astype(np.int32) if v else np.zeros(0, np.int32) for k, v in cols.items()}, S, B
+    import torch
+    if max(N, 2 * R) > (2 ** 31 - 1) // 2:
+        raise ValueError("csr_from_rows_batch: the batch is too large for int32 indices")
+    L = nat.lib()
+    cat = lambda i: np.concatenate([p[i] for p in parts]) if parts else np.zeros(0, np.int64)  # noqa: E731
+    t_ids, t_a, t_b = (torch.from_numpy(cat(i)).to(device) for i in range(3))
+    shapes = {"order": max(N, 1), "sub_id": max(N, 1), "slot_ptr": N + 1, "out_ptr": N + 1,
+              "slot_src": max(2 * R, 1), "tse_rank": max(2 * R, 1), "out_slot": max(2 * R, 1)}
+    o = {k: torch.zeros(n, dtype=torch.int32, device=device) for k, n in shapes.items()}
+    event = torch.zeros(max(N, 1), dtype=torch.int32, device=device)
+    ws_bytes = int(L.gtf_build_events_device_workspace_bytes(N, R, K))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    no, ro = node_off.astype(np.int32), row_off.astype(np.int32)
+    ev = nat.GtfEventCsr(N, R, vp(t_ids) if N else None, vp(t_a) if R else None, vp(t_b) if R else None,
+                         *[vp(o[k]) for k in BATCH_CSR], 0, 0, 0)
+    bt = nat.GtfEventBatch(n_events=K, node_off=no.ctypes.data, row_off=ro.ctypes.data, event=vp(event))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    nat.check(L.gtf_build_events_csr_device(ctypes.byref(ev), ctypes.byref(bt), vp(ws), ws_bytes, stream))
+    E, n_sub = int(ev.n_edges), int(ev.n_subgraphs)
+    size = {"order": N, "sub_id": N, "slot_ptr": N + 1, "out_ptr": N + 1, "slot_src": E, "tse_rank": E, "out_slot": E}
+    out = {k: o[k][:size[k]].cpu().numpy() for k in BATCH_CSR}
+    out["event"] = event[:N].cpu().numpy()
+    return out, E, n_sub
+
+
 def build_event_csr(event_prefix: str, min_volume: int, max_volume: int, device=None):
     """Event conversion's graph straight to the packed CSR (gtf_build_event_csr, or on
     the GPU with ``device``: gtf_build_event_csr_device): the same TrackGraph as pack()

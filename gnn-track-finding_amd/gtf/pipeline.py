@@ -126,9 +126,18 @@ def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Para
     domain (csvdev.OutOfDomain) is read by the host reader instead; ``d.parse_info`` says which
     parser read each file ({"nodes": "device" | "host", "edges": ...}, with "nodes_reason" /
     "edges_reason" after a fallback). The same graph either way, bit for bit."""
-    from . import io
     from .device import DeviceGraph
     p = p or Params()
+    cols, info = _event_columns(event_prefix, min_volume, max_volume, device, mem, parse)
+    d = DeviceGraph.from_event(*cols, device, mem)
+    d.parse_info = info
+    return _event_states(d, p)
+
+
+def _event_columns(event_prefix, min_volume, max_volume, device, mem, parse):
+    """from_event's eight columns of one event's files, by the host readers or the device parser
+    (build_event_dev's ``parse``), and which parser read each file"""
+    from . import io
     if parse not in ("host", "device"):
         raise ValueError("parse must be 'host' or 'device'")
     info = {"nodes": "host", "edges": "host"}
@@ -155,8 +164,12 @@ def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Para
         except OutOfDomain as e:
             info["edges_reason"] = str(e)
             n2, n1 = (mm.from_host(a) for a in io.read_edges(event_prefix + "edges.csv"))
-    d = DeviceGraph.from_event(ids, x, y, z, r, layer, n1, n2, device, mem)
-    d.parse_info = info
+    return (ids, x, y, z, r, layer, n1, n2), info
+
+
+def _event_states(d, p):
+    """the states, priors, mixture weights, degrees and send weights of a fresh from_event /
+    from_events graph (event_conversion.py:86-101), on that object"""
     if d.n_nodes == 0:
         return d
     d.clear_errors()
@@ -165,6 +178,22 @@ def build_event_dev(event_prefix: str, min_volume: int, max_volume: int, p: Para
     d.raise_errors()
     d.refresh_send_mw()
     return d
+
+
+def build_events_dev(prefixes, min_volume: int, max_volume: int, p: Params = None, device="cuda",
+                     mem: str = "torch", parse: str = "host"):
+    """build_event_dev for a batch of events in ONE build: every event's files are read as
+    build_event_dev reads them (the device parse and its per-file host fallback stay per file;
+    ``parse_info`` is the list of the events' records), DeviceGraph.from_events makes the fused graph --
+    what DeviceGraph.concat of the events' build_event_dev graphs holds, bit for bit -- and the states,
+    priors, mixture weights, degrees and send weights are computed ONCE on it. run_batch(d) runs the
+    loop on it without a concat; d.n_events and d.event_nodes say how it divides."""
+    from .device import DeviceGraph
+    p = p or Params()
+    read = [_event_columns(prefix, min_volume, max_volume, device, mem, parse) for prefix in prefixes]
+    d = DeviceGraph.from_events([cols for cols, _ in read], device, mem)
+    d.parse_info = [info for _, info in read]
+    return _event_states(d, p)
 
 
 def _ids(g: TrackGraph, groups):
@@ -198,12 +227,19 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
     graphs after each step -- as in run(), a record's remaining_graph ends holding the next stage's
     output and merged coordinates.
     A reference exception (DeviceGraph.raise_errors) in any event raises here as it does in run(); the
-    error word is the fused graph's, so the message does not say which event."""
+    error word is the fused graph's, so the message does not say which event.
+    ``ds`` may also be ONE fused graph as build_events_dev returns it (DeviceGraph.from_events: it holds
+    ``event_nodes``): the loop starts on it without a concat, the events' node counts are its
+    ``event_nodes`` and keep_graphs takes its own host_graph(). The same records; iteration ``first``
+    runs on that object, as run() runs on a DeviceGraph input."""
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
-    ds = list(ds)
-    K = len(ds)
+    fused = ds if isinstance(ds, DeviceGraph) else None
+    if fused is not None and not hasattr(fused, "event_nodes"):
+        raise ValueError("run_batch takes a list of resident events or one fused graph of build_events_dev")
+    ds = [fused] if fused is not None else list(ds)
+    K = fused.n_events if fused is not None else len(ds)
     if scorers is not None and len(scorers) != K:
         raise ValueError("scorers must hold one entry (a DeviceScorer or None) per event")
     for g in ds:
@@ -215,9 +251,13 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
     if K == 0:
         return out
     t0 = time.perf_counter()
-    d = DeviceGraph.concat(ds)
-    left = [g.n_nodes for g in ds]   # the nodes every event enters the iteration with
-    G = concat([g.host_graph()[0] for g in ds]) if keep_graphs else None   # the fused graph's host copy
+    d = fused if fused is not None else DeviceGraph.concat(ds)
+    # the nodes every event enters the iteration with
+    left = list(fused.event_nodes) if fused is not None else [g.n_nodes for g in ds]
+    if fused is not None:
+        G = fused.host_graph()[0] if keep_graphs else None
+    else:
+        G = concat([g.host_graph()[0] for g in ds]) if keep_graphs else None   # the fused graph's host copy
     last = first + iterations - 1
     for it in range(first, first + iterations):
         if d.n_nodes == 0:

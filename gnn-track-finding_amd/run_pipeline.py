@@ -35,6 +35,9 @@ the device parser's exact domain is read by the host reader. The same files eith
 scored on the GPU as with --resident-metrics. Event i's files go under ROOTDIR/<i>/ in the layout above, the
 same files a single run of that event writes. If a stage raises a reference exception the whole batch
 stops; the message does not say which event.
+--batch-build (with --batch) builds the events in ONE call (pipeline.build_events_dev:
+gtf_build_events_csr_device on the concatenated columns) instead of once per event followed by the concat:
+the same files under ROOTDIR/<i>/.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -144,6 +147,9 @@ def main(argv=None):
     ap.add_argument("--batch", nargs="+", metavar="DIR",
                     help="several event_network directories: the events are built in GPU memory, fused and run as one "
                          "loop (pipeline.run_batch); event i's outputs go under ROOTDIR/<i>/; only with --start 1")
+    ap.add_argument("--batch-build", action="store_true",
+                    help="with --batch: one graph build for all events (pipeline.build_events_dev) instead of one "
+                         "per event and a concat; the same files")
     ap.add_argument("--truth", nargs="+", metavar="DIR",
                     help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py); with --batch one "
                          "directory for every event, or one per event")
@@ -160,6 +166,8 @@ def main(argv=None):
             ap.error("--batch converts the events: only with --start 1")
         if args.eventNetwork:
             ap.error("--batch names the event directories itself: not with -n")
+    if args.batch_build and not args.batch:
+        ap.error("--batch-build builds the events of --batch")
     if args.resident_parse:
         args.resident_event = True
     if args.resident_event and args.start != 1:
@@ -254,7 +262,29 @@ def _metrics(args, root, its, scorers, truth_dir):
 def _batch(args, p, ex):
     """--batch: the events built in GPU memory, one fused loop, event i's files under ROOTDIR/<i>/"""
     devs, times = [], []
-    for i, dn in enumerate(args.batch):
+    if args.batch_build:
+        import numpy as np
+        from gtf.graph import split_events
+        t0 = time.perf_counter()
+        fused = pipeline.build_events_dev([os.path.join(dn, "event_1_filtered_graph_") for dn in args.batch],
+                                          args.min_volume, args.max_volume, p, args.device,
+                                          parse="device" if args.resident_parse else "host")
+        if args.resident_parse:
+            for info in fused.parse_info:
+                for key in ("nodes", "edges"):
+                    _parser_line(key, info)
+        G, vivl = fused.host_graph()
+        event = fused._np(fused.carried["event"])
+        cut = np.searchsorted(event, np.arange(len(args.batch) + 1))
+        seconds = (time.perf_counter() - t0) / max(len(args.batch), 1)   # (one build: every event its share)
+        for i, g in enumerate(split_events(G, event, len(args.batch))):
+            times.append({"event_conversion": seconds})
+            store.save_graph(os.path.join(_dir(args.outputDir, str(i), "track_sim", "network"), "graph.npz"), g,
+                             vivl[cut[i]:cut[i + 1]])
+            print("event %d conversion: %d nodes, %d directed edges, %d subgraphs (%.3f s)"
+                  % (i, g.n_nodes, g.n_edges, g.n_subgraphs, seconds))
+        devs = fused
+    for i, dn in enumerate(() if args.batch_build else args.batch):
         t0 = time.perf_counter()
         dev = pipeline.build_event_dev(os.path.join(dn, "event_1_filtered_graph_"), args.min_volume, args.max_volume, p,
                                        args.device, parse="device" if args.resident_parse else "host")
@@ -267,9 +297,9 @@ def _batch(args, p, ex):
         print("event %d conversion: %d nodes, %d directed edges, %d subgraphs (%.3f s)"
               % (i, g.n_nodes, g.n_edges, g.n_subgraphs, times[i]["event_conversion"]))
         devs.append(dev)
-    truth = [None] * len(devs)
+    truth = [None] * len(args.batch)
     if args.truth_dirs:
-        truth = args.truth_dirs if len(args.truth_dirs) > 1 else args.truth_dirs * len(devs)
+        truth = args.truth_dirs if len(args.truth_dirs) > 1 else args.truth_dirs * len(args.batch)
     scorers = [_scorers(args, t) if t else None for t in truth]
     its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=scorers if args.truth_dirs else None,
                              first=1, keep_graphs=True)

@@ -1046,6 +1046,46 @@ int gtf_build_event_csr(gtf_event_csr* ev);
 size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows);
 int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
 
+/* A batch of K events in ONE build (gtf_build_dev.hip): replaces running event_conversion.py
+ * (:53-101; helper.construct_graph, helper.py:465-521) once per event and fusing the results
+ * (gtf/graph.py concat). *ev is gtf_event_csr with the events' columns laid end to end in
+ * event order -- n_nodes = N and n_rows = R the sums, node_id / row_a / row_b and the seven
+ * outputs DEVICE arrays at the summed sizes -- and *b says where each event starts. The result
+ * is gtf_build_event_csr of every event, shifted by the sizes of the events before it as
+ * gtf_graph_concat shifts: order and slot_src by the nodes before, sub_id by the subgraphs,
+ * slot_ptr and out_slot by the slots, out_ptr by the edges, tse_rank as it is; n_edges and
+ * n_subgraphs are the batch's. Node ids are looked up inside their own event: the same id
+ * (the same event twice) may appear in any number of events, a row end that its own event
+ * does not hold drops the row even if another event holds that id, a repeated id is an error
+ * inside one event only (the message names the first such event), and the 2|c| >= |G| rule
+ * of the node order counts the nodes of the component's own event. Event e's packed nodes
+ * are the positions [node_off[e], node_off[e+1]). Events without nodes, without rows, or
+ * with rows that are all dropped are legal anywhere.
+ * Synchronises `stream` as often as gtf_build_event_csr_device does for one event: the count
+ * does not grow with K, and the component rounds are the deepest event's, not their sum. */
+typedef struct gtf_event_batch {
+    uint32_t struct_size;      /* sizeof(gtf_event_batch) as the caller compiled it */
+    uint32_t abi_version;      /* GTF_ABI_VERSION */
+    int32_t n_events;          /* K >= 0 */
+    int32_t pad_;
+    const int32_t* node_off;   /* HOST [K+1]: event e's nodes are [node_off[e], node_off[e+1]); 0 first, N last */
+    const int32_t* row_off;    /* HOST [K+1]: the same for the edge rows; 0 first, R last */
+    int32_t* event;            /* out, DEVICE [N] or NULL: the event of every packed node */
+} gtf_event_batch;
+
+/* includes the two offset tables, which the call uploads; non-decreasing in every argument */
+size_t gtf_build_events_device_workspace_bytes(int64_t n_nodes, int64_t n_rows, int32_t n_events);
+
+/* -3: *b built against another layout of this header (struct_size, abi_version).
+ * -2, decided on the host before any launch: a NULL ev, b, offset table, workspace or array
+ * that the sizes need; offsets that do not start at 0, decrease, or end elsewhere than at
+ * n_nodes / n_rows; n_nodes or 2 * n_rows above INT32_MAX / 2; a workspace below
+ * gtf_build_events_device_workspace_bytes. -2 after the first synchronisation: a node id
+ * outside [0, 2^61 - 1), a repeated id inside one event. The kernels of this call clamp every
+ * write to the outputs' sizes. */
+int gtf_build_events_csr_device(gtf_event_csr* ev, const gtf_event_batch* b, void* workspace, size_t workspace_bytes,
+                                gtf_stream_t stream);
+
 /* ---- event conversion: the packed event's columns and empty states, on the GPU --------
  * What is left of event conversion between the CSR above and gtf_track_state_estimates:
  * the node attributes construct_graph stores (helper.py:465-545: GNN_Measurement, xyzr,

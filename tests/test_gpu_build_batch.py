@@ -1,0 +1,348 @@
+"""A batch of events built in one call (gtf_build_events_csr_device, io.csr_from_rows_batch,
+DeviceGraph.from_events, pipeline.build_events_dev, run_batch on the fused graph, run_pipeline.py
+--batch-build) against what it replaces: the host builder once per event with gtf.graph.concat's offsets
+(io.csr_from_rows_batch(device=None), pinned by tests/test_build_batch_cases.py), DeviceGraph.concat of the
+events' from_event / build_event_dev graphs, and run_batch on the list. Everything is exact: the batch
+build moves the same integers, and every later kernel sees the same per-node inputs."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import batch_cases as bc
+import build_batch_cases as bb
+import real800 as R
+from gtf import _native as nat
+from gtf import io
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 256   # (a multiple of the arena's alignment: the workspace between its guards stays aligned)
+KEYS = io.BATCH_CSR
+BATCH = [("vol7",), ("hand", "perm257"), ("empty",), ("vol7",)]   # the list tests/test_gpu_batch.py runs
+
+
+# ---------------------------------------------------------------- 1. the C-ABI between guard bytes
+class _Mem:
+    """device buffers of one allocator: "torch" tensors or "hip" (gtf.devmem) arrays"""
+
+    def __init__(self, mem):
+        self.mem = mem
+        if mem == "torch":
+            import torch
+            self.torch = torch
+            self.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        else:
+            self.stream = ctypes.c_void_p(0)
+
+    def up(self, a):
+        a = np.ascontiguousarray(a).reshape(-1)
+        if self.mem == "torch":
+            return self.torch.from_numpy(a).cuda()
+        from gtf.devmem import HipArray
+        return HipArray.from_numpy(a)
+
+    def host(self, t):
+        return t.cpu().numpy() if self.mem == "torch" else t.numpy()
+
+    def guarded(self, nbytes):
+        return self.up(np.full(GUARD + nbytes + GUARD, 0xA5, np.uint8))
+
+    def payload(self, t, nbytes, dtype=np.int32):
+        h = self.host(t)
+        assert bool((h[:GUARD] == 0xA5).all()) and bool((h[GUARD + nbytes:] == 0xA5).all()), "guard bytes"
+        return h[GUARD:GUARD + nbytes].view(dtype)
+
+
+def _abi(parts, mem, tamper=None, ws_short=0):
+    """gtf_build_events_csr_device on raw buffers: every output, the event column and the workspace lie
+    between guard bytes. Returns (status, outputs as host arrays at their allocated sizes, n_edges, n_sub)."""
+    L = nat.lib()
+    m = _Mem(mem)
+    K = len(parts)
+    node_off = np.concatenate([[0], np.cumsum([p[0].size for p in parts])]).astype(np.int32)
+    row_off = np.concatenate([[0], np.cumsum([p[1].size for p in parts])]).astype(np.int32)
+    N, Rr = int(node_off[-1]), int(row_off[-1])
+    cat = lambda i: np.concatenate([p[i] for p in parts] + [np.zeros(1, np.int64)])  # noqa: E731 (never empty)
+    ids, a, b = (m.up(cat(i)) for i in range(3))
+    size = {"order": N, "sub_id": N, "slot_ptr": N + 1, "out_ptr": N + 1, "slot_src": 2 * Rr, "tse_rank": 2 * Rr,
+            "out_slot": 2 * Rr, "event": N}
+    out = {k: m.guarded(4 * n) for k, n in size.items()}
+    nb = int(L.gtf_build_events_device_workspace_bytes(N, Rr, K))
+    ws = m.guarded(nb)
+    at = lambda t: ctypes.c_void_p(t.data_ptr() + GUARD)  # noqa: E731
+    ev = nat.GtfEventCsr(N, Rr, ids.data_ptr(), a.data_ptr(), b.data_ptr(), *[at(out[k]) for k in KEYS], 0, 0, 0)
+    bt = nat.GtfEventBatch(n_events=K, node_off=node_off.ctypes.data, row_off=row_off.ctypes.data, event=at(out["event"]))
+    if tamper:
+        tamper(ev, bt, node_off, row_off)
+    rc = L.gtf_build_events_csr_device(ctypes.byref(ev), ctypes.byref(bt), at(ws), ctypes.c_size_t(nb - ws_short), m.stream)
+    got = {k: m.payload(out[k], 4 * n) for k, n in size.items()}
+    m.payload(ws, nb, np.uint8)
+    return rc, got, int(ev.n_edges), int(ev.n_subgraphs)
+
+
+@pytest.mark.parametrize("mem", ["torch", "hip"])
+@pytest.mark.parametrize("name", list(bb.CASES))
+def test_batch_build_abi_equals_the_host_definition(name, mem):
+    exp, E, B = bb.reference(name)
+    rc, got, e, b = _abi(bb.CASES[name], mem)
+    assert rc == 0, nat.lib().gtf_last_error()
+    assert (e, b) == (E, B)
+    for k in KEYS + ("event",):
+        assert got[k].dtype == exp[k].dtype and np.array_equal(got[k][:exp[k].size], exp[k]), k
+    for k in ("slot_src", "tse_rank", "out_slot"):      # beyond the kept edges nothing is written
+        assert bool((got[k][E:].view(np.uint8) == 0xA5).all()), k
+
+
+def test_batch_build_binding_equals_the_host_definition():
+    for name in ("half_size", "rows_no_nodes", "all_empty", "tiny257"):
+        exp, E, B = bb.reference(name)
+        got, e, b = io.csr_from_rows_batch(bb.CASES[name], device="cuda")
+        assert (e, b) == (E, B) and sorted(got) == sorted(exp)
+        for k in exp:
+            assert got[k].dtype == exp[k].dtype and np.array_equal(got[k], exp[k]), (name, k)
+
+
+def test_duplicate_id_inside_an_event_names_it():
+    rc, _, _, _ = _abi(bb.DUP_INSIDE, "torch")
+    assert rc == -2 and b"duplicate node id in event 1" in nat.lib().gtf_last_error()
+    with pytest.raises(RuntimeError, match="duplicate node id in event 1"):
+        io.csr_from_rows_batch(bb.DUP_INSIDE, device="cuda")
+    rc, _, _, _ = _abi([bb.part([1, 2]), bb.part([3, -4])], "torch")
+    assert rc == -2 and b"2^61" in nat.lib().gtf_last_error()
+
+
+def _untouched(got):
+    return all(bool((v.view(np.uint8) == 0xA5).all()) for v in got.values())
+
+
+def test_host_refusals_leave_the_outputs_untouched():
+    parts = bb.CASES["half_size"]
+    L = nat.lib()
+
+    def refused(tamper=None, ws_short=0, status=-2, text=b"gtf_build_events_csr_device"):
+        rc, got, _, _ = _abi(parts, "torch", tamper, ws_short)
+        assert rc == status and text in L.gtf_last_error() and _untouched(got), (rc, L.gtf_last_error())
+
+    refused(ws_short=1, text=b"workspace")
+
+    def decreasing(ev, bt, no, ro):
+        no[1], no[2] = no[2], no[1] - 1
+    refused(decreasing, text=b"decrease")
+
+    def rows_decreasing(ev, bt, no, ro):
+        ro[2] = ro[1] - 1
+    refused(rows_decreasing, text=b"decrease")
+
+    def first(ev, bt, no, ro):
+        no[0] = 1
+    refused(first, text=b"start at 0")
+
+    def node_end(ev, bt, no, ro):
+        no[-1] -= 1
+    refused(node_end, text=b"end at")
+
+    def row_end(ev, bt, no, ro):
+        ro[-1] += 1
+    refused(row_end, text=b"end at")
+
+    def too_large(ev, bt, no, ro):
+        ev.n_nodes = (2 ** 31 - 1) // 2 + 1
+    refused(too_large, text=b"too large")
+
+    def rows_too_large(ev, bt, no, ro):
+        ev.n_rows = (2 ** 31 - 1) // 4 + 1
+    refused(rows_too_large, text=b"too large")
+
+    def null_offsets(ev, bt, no, ro):
+        bt.row_off = None
+    refused(null_offsets, text=b"bad arguments")
+
+    def null_output(ev, bt, no, ro):
+        ev.sub_id = None
+    refused(null_output, text=b"bad arguments")
+
+    def negative_events(ev, bt, no, ro):
+        bt.n_events = -1
+    refused(negative_events, text=b"bad arguments")
+
+    def other_abi(ev, bt, no, ro):
+        bt.abi_version = nat.ABI_VERSION - 1
+    refused(other_abi, status=-3, text=b"gtf_event_batch ABI mismatch")
+
+    def other_size(ev, bt, no, ro):
+        bt.struct_size += 8
+    refused(other_size, status=-3, text=b"gtf_event_batch ABI mismatch")
+    fake = ctypes.c_void_p(256)
+    ev = nat.GtfEventCsr()
+    assert L.gtf_build_events_csr_device(ctypes.byref(ev), None, fake, 256, None) == -2
+    assert L.gtf_build_events_csr_device(None, ctypes.byref(nat.GtfEventBatch()), fake, 256, None) == -2
+    sizes = [L.gtf_build_events_device_workspace_bytes(100, 100, k) for k in (0, 1, 64, 4096)]
+    assert sizes == sorted(sizes) and sizes[0] >= L.gtf_build_event_device_workspace_bytes(100, 100)
+
+
+# ---------------------------------------------------------------- 2. from_events against concat of from_events
+def _bits(x):
+    """a host array as bytes (a NaN is its bits)"""
+    return np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+
+
+def _resident_equal(got, exp, what):
+    """every array of .t (the workspace apart: scratch), every carried column and every size, as bytes.
+    out_sched and out_lanes are allocated at their capacity and uninitialised beyond what gtf_graph_prepare
+    writes (tests/test_gpu_graph_subset.py _assert_tables_equal): their written entries are compared."""
+    for k in ("n_nodes", "n_slots", "n_edges", "n_sub", "n_events", "tables", "layout", "mem"):
+        assert getattr(got, k) == getattr(exp, k), (what, k)
+    assert sorted(got.t) == sorted(exp.t), what
+    assert sorted(got.carried) == sorted(exp.carried) == ["event", "vivl"], what
+    written = {}
+    if hasattr(exp, "cg_sched"):
+        n_o = [exp.cg_sched.n_o4, exp.cg_sched.n_o8, exp.cg_sched.n_o16]
+        assert n_o == [got.cg_sched.n_o4, got.cg_sched.n_o8, got.cg_sched.n_o16], what
+        written = {"out_sched": 4 * sum(n_o), "out_lanes": 2 * (4 * n_o[0] + 8 * n_o[1])}
+    for name, a, b in [(k, got.t[k], exp.t[k]) for k in exp.t if k != "ws"] + \
+                      [(k, got.carried[k], exp.carried[k]) for k in exp.carried]:
+        x, y = got._np(a), exp._np(b)
+        n = min(written.get(name, y.size), y.size)
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(_bits(x[:n]), _bits(y[:n])), (what, name)
+
+
+@pytest.mark.parametrize("mem,where", [("torch", "host"), ("torch", "device"), ("hip", "host"), ("hip", "device")])
+def test_from_events_equals_concat_of_from_events(mem, where):
+    from gtf.device import DeviceGraph
+    from gtf.metrics import _Mem as DevMem
+    cols = [bc.columns(s) for s in BATCH]
+    exp = DeviceGraph.concat([DeviceGraph.from_event(*c, mem=mem) for c in cols], mem=mem)
+    if where == "device":
+        mm = DevMem("cuda", mem)
+        given = [tuple(mm.from_host(np.ascontiguousarray(a, np.int64 if i in (0, 5, 6, 7) else np.float64))
+                       for i, a in enumerate(c)) for c in cols]
+    else:
+        given = cols
+    got = DeviceGraph.from_events(given, mem=mem)
+    assert got.event_nodes == [8748, 257, 0, 8748] and got.n_events == 4
+    _resident_equal(got, exp, (mem, where))
+    h, v = got.host_graph()
+    he, ve = exp.host_graph()
+    from test_gpu_event_pack import _graphs_equal
+    _graphs_equal(h, he, (mem, where))
+    assert np.array_equal(_bits(v), _bits(ve))
+
+
+def test_from_events_edge_lists():
+    from gtf.device import DeviceGraph
+    e = DeviceGraph.from_events([])
+    assert (e.n_nodes, e.n_slots, e.n_edges, e.n_sub, e.n_events, e.event_nodes) == (0, 0, 0, 0, 0, [])
+    e = DeviceGraph.from_events([bc.columns(("empty",))] * 2)
+    assert (e.n_nodes, e.n_events, e.event_nodes) == (0, 2, [0, 0]) and e.carried["event"].numel() == 0
+    one = DeviceGraph.from_events([bc.columns(("hand", "two"))])
+    _resident_equal(one, DeviceGraph.concat([DeviceGraph.from_event(*bc.columns(("hand", "two")))]), "K = 1")
+    with pytest.raises(ValueError, match="eight columns"):
+        DeviceGraph.from_events([bc.columns(("hand", "two"))[:7]])
+
+
+# ---------------------------------------------------------------- 3. build_events_dev, run_batch on the fused graph
+@pytest.fixture(scope="module")
+def event_dirs(tmp_path_factory):
+    """--eventNetwork directories of the BATCH list: the vol-7 fixture, and the hand-made events written as CSVs"""
+    out = []
+    for i, spec in enumerate(BATCH):
+        if spec == ("vol7",):
+            out.append(os.path.join(bc.GOLDEN, "kat134"))
+            continue
+        d = str(tmp_path_factory.mktemp("ev%d" % i))
+        ids, x, y, z, r, layer, a, b = bc.columns(spec)
+        with open(os.path.join(d, "event_1_filtered_graph_nodes.csv"), "w") as f:
+            f.write("node_idx,layer_id,x,y,z\n")
+            for k in range(ids.size):
+                f.write("%d,%d,%r,%r,%r\n" % (ids[k], layer[k], float(x[k]), float(y[k]), float(z[k])))
+        with open(os.path.join(d, "event_1_filtered_graph_edges.csv"), "w") as f:
+            f.write("%d %d\nnode2,node1,weight\n" % (ids.size, a.size))
+            for k in range(a.size):
+                f.write("%d,%d,1.0\n" % (b[k], a[k]))
+        out.append(d)
+    return out
+
+
+def _prefixes(dirs):
+    return [os.path.join(d, "event_1_filtered_graph_") for d in dirs]
+
+
+def test_build_events_dev_equals_concat_of_build_event_devs(event_dirs):
+    """the same kernels see the same per-node inputs: every field bit for bit (floats through their bytes)"""
+    from gtf import pipeline
+    from gtf.device import DeviceGraph
+    exp = DeviceGraph.concat([pipeline.build_event_dev(p, 7, 8) for p in _prefixes(event_dirs)])
+    got = pipeline.build_events_dev(_prefixes(event_dirs), 7, 8)
+    assert got.parse_info == [{"nodes": "host", "edges": "host"}] * 4 and got.event_nodes[0] == 8748
+    _resident_equal(got, exp, "build_events_dev")
+    assert np.isnan(got._np(got.t["tse_mw"])).sum() == np.isnan(exp._np(exp.t["tse_mw"])).sum()
+
+
+def test_run_batch_on_the_fused_graph_equals_the_list(event_dirs):
+    from gtf import metrics, pipeline
+    from test_gpu_batch import _records_equal
+    from test_gpu_score import golden
+    pre = _prefixes(event_dirs)
+    vol7 = [s == ("vol7",) for s in BATCH]
+    sa = [metrics.DeviceScorer(golden()[3]) if v else None for v in vol7]
+    sb = [metrics.DeviceScorer(golden()[3]) if v else None for v in vol7]
+    exp = pipeline.run_batch([pipeline.build_event_dev(p, 7, 8) for p in pre], iterations=3, scorers=sa)
+    got = pipeline.run_batch(pipeline.build_events_dev(pre, 7, 8), iterations=3, scorers=sb)
+    assert len(got) == len(exp) == 4 and got[2] == []
+    for e in range(4):
+        assert len(got[e]) == len(exp[e])
+        _records_equal(got[e], exp[e], e)
+    for e in (0, 3):
+        assert [len(r.candidates) for r in got[e]] == [1055, 110, 2]
+        r = sb[e].result()
+        assert (r.n_reconstructed, r.n_reference) == (133, 163)
+    with pytest.raises(ValueError, match="fused graph"):
+        pipeline.run_batch(pipeline.build_event_dev(pre[1], 7, 8))
+    with pytest.raises(ValueError, match="per event"):
+        pipeline.run_batch(pipeline.build_events_dev(pre[1:3], 7, 8), scorers=[None])
+
+
+def test_build_events_dev_parse_device_equals_parse_host():
+    from gtf import pipeline
+    pre = [os.path.join(bc.GOLDEN, "kat134", "event_1_filtered_graph_"), R.PREFIX]
+    a = pipeline.build_events_dev(pre, 7, 8, parse="host")
+    b = pipeline.build_events_dev(pre, 7, 8, parse="device")
+    assert b.parse_info == [{"nodes": "device", "edges": "device"}] * 2 and a.event_nodes[0] == 8748
+    assert a.event_nodes[1] > 0
+    _resident_equal(b, a, "parse=device")
+
+
+# ---------------------------------------------------------------- 4. the CLI
+def test_gpu_pipeline_cli_batch_build(tmp_path, event_dirs):
+    """run_pipeline.py --batch A B --batch-build writes the files --batch A B writes"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cli = os.path.join(root, "gnn-track-finding_amd", "run_pipeline.py")
+    dirs = event_dirs[:2]
+    common = ["-a", "7", "-z", "8"]
+    a, b = str(tmp_path / "loop"), str(tmp_path / "built")
+    subprocess.check_call([sys.executable, cli, "--batch"] + dirs + ["-o", a] + common)
+    subprocess.check_call([sys.executable, cli, "--batch"] + dirs + ["-o", b, "--batch-build"] + common)
+    files = sorted(os.path.relpath(os.path.join(r, f), a) for r, _, fs in os.walk(a) for f in fs)
+    assert files == sorted(os.path.relpath(os.path.join(r, f), b) for r, _, fs in os.walk(b) for f in fs)
+    assert sum(f.endswith(".npz") for f in files) >= 2 * (1 + 4) and all(f[0] in "01" for f in files)
+    for f in files:
+        x, y = os.path.join(a, f), os.path.join(b, f)
+        if f.endswith(".npz"):
+            with np.load(x) as zx, np.load(y) as zy:
+                assert sorted(zx.files) == sorted(zy.files), f
+                for k in zx.files:
+                    assert zx[k].dtype == zy[k].dtype and zx[k].shape == zy[k].shape and \
+                        np.array_equal(_bits(zx[k]), _bits(zy[k])), (f, k)
+        elif f.endswith(".csv"):
+            assert open(x).read() == open(y).read(), f
+        else:
+            assert f.endswith("timings.json"), f
+            assert sorted(json.load(open(x))) == sorted(json.load(open(y)))
+    rc = subprocess.run([sys.executable, cli, "-n", dirs[0], "-o", str(tmp_path / "x"), "--batch-build"],
+                        capture_output=True, text=True)
+    assert rc.returncode == 2 and "--batch" in rc.stderr
