@@ -162,6 +162,48 @@ class GtfScoreCounts(ctypes.Structure):
 SCORE_ERR_MISSING, SCORE_ERR_WORKSPACE, SCORE_ERR_RANGE = 1, 2, 4   # GTF_SCORE_ERR_*
 
 
+class GtfTruthBatch(ctypes.Structure):
+    """gtf_truth_batch: K events' truth tables end to end on the device; keyword construction only --
+    struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_events", I32), ("n_nodes", I32), ("n_entries", I32),
+                ("n_particles", I32), ("node_off", P), ("entry_off", P), ("part_off", P), ("node_id", P),
+                ("node_ptr", P), ("node_part", P), ("part_id", P), ("part_hits", P), ("part_ref", P), ("scored", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfTruthBatch)
+        self.abi_version = ABI_VERSION
+
+
+class GtfTruthSizes(ctypes.Structure):
+    """gtf_truth_sizes: the sizes of one part of gtf_truth_concat (a host array)"""
+    _fields_ = [("n_nodes", I32), ("n_entries", I32), ("n_particles", I32), ("pad_", I32)]
+
+
+class GtfTruthPart(ctypes.Structure):
+    """gtf_truth_part: one entry of gtf_truth_concat's device table"""
+    _fields_ = [("n_nodes", I32), ("n_entries", I32), ("n_particles", I32), ("pad_", I32), ("node_id", P),
+                ("node_ptr", P), ("node_part", P), ("part_id", P), ("part_hits", P), ("part_ref", P)]
+
+
+class GtfTruthBatchBuf(ctypes.Structure):
+    """gtf_truth_batch_buf: the caller-allocated outputs of gtf_truth_concat"""
+    _fields_ = [("node_off", P), ("entry_off", P), ("part_off", P), ("node_id", P), ("node_ptr", P),
+                ("node_part", P), ("part_id", P), ("part_hits", P), ("part_ref", P)]
+
+
+class GtfScoreStateEv(ctypes.Structure):
+    """gtf_score_state_ev: the per-particle claims of a whole batch; keyword construction only --
+    struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_particles", I32), ("pad_", I32), ("best_key", P),
+                ("best_good", P), ("best_total", P), ("error", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfScoreStateEv)
+        self.abi_version = ABI_VERSION
+
+
 class GtfTruthIn(ctypes.Structure):
     """gtf_truth_in: the parsed columns gtf_truth_build reads, device arrays; keyword construction
     only -- struct_size / abi_version are filled in (another layout: status -3)"""
@@ -400,6 +442,9 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
            "gtf_score_reset", "gtf_score_workspace_bytes", "gtf_score_candidates",
            "gtf_score_finish_workspace_bytes", "gtf_score_finish",
+           "gtf_truth_concat_workspace_bytes", "gtf_truth_concat", "gtf_score_reset_ev",
+           "gtf_score_ev_workspace_bytes", "gtf_score_candidates_ev",
+           "gtf_score_finish_ev_workspace_bytes", "gtf_score_finish_ev",
            "gtf_truth_build_workspace_bytes", "gtf_truth_build",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_build_events_device_workspace_bytes", "gtf_build_events_csr_device",
@@ -502,6 +547,18 @@ def lib(lean: bool = False):
     L.gtf_score_finish_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_score_finish_workspace_bytes.argtypes = [I32]
     L.gtf_score_finish.argtypes = [TR, SS, P, P, P, P, P, ctypes.POINTER(GtfScoreCounts), P, ctypes.c_size_t, P]
+    TB, SE = ctypes.POINTER(GtfTruthBatch), ctypes.POINTER(GtfScoreStateEv)
+    L.gtf_truth_concat_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_truth_concat_workspace_bytes.argtypes = [I32]
+    L.gtf_truth_concat.argtypes = [ctypes.POINTER(GtfTruthSizes), P, I32, ctypes.POINTER(GtfTruthBatchBuf), TB, P,
+                                   ctypes.c_size_t, P]
+    L.gtf_score_reset_ev.argtypes = [SE, TB, P, P]
+    L.gtf_score_ev_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_score_ev_workspace_bytes.argtypes = [I32, I32, I32]
+    L.gtf_score_candidates_ev.argtypes = [TB, P, P, P, I32, I32, ctypes.POINTER(GtfScoreOut), SE, P, ctypes.c_size_t, P]
+    L.gtf_score_finish_ev_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_score_finish_ev_workspace_bytes.argtypes = [I32, I32]
+    L.gtf_score_finish_ev.argtypes = [TB, SE, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     L.gtf_truth_build_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_truth_build_workspace_bytes.argtypes = [I32, I32, I32]
     L.gtf_truth_build.argtypes = [ctypes.POINTER(GtfTruthIn), ctypes.POINTER(GtfTruthBuf), TR,
@@ -590,7 +647,8 @@ def lib(lean: bool = False):
                "gtf_extract_outputs", "gtf_event_pack", "gtf_fill_columns", "gtf_score_reset",
                "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
-               "gtf_event_split", "gtf_build_events_csr_device"):
+               "gtf_event_split", "gtf_build_events_csr_device", "gtf_truth_concat", "gtf_score_reset_ev",
+               "gtf_score_candidates_ev", "gtf_score_finish_ev"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -253,7 +253,8 @@ def split_dev(d, o, n_events=None):
     ids=True, lists=False, members=True). Returns {"first": {"cand" | "rem" | "frag": host int32
     [K + 1], the first group of every event in that list}, "counts": K dicts of the six counts,
     "cand_ptr_ev": the device array of every event's candidate pointers rebased to 0, event e's at
-    first["cand"][e] + e}. One small download after the call's own synchronisation. Raises
+    first["cand"][e] + e, "cand_first_dev": a device view of first["cand"], the K + 1 words the call
+    wrote (metrics.BatchScorer.add's cand_first)}. One small download after the call's own synchronisation. Raises
     RuntimeError (rc -2) when a group spans two events or the events do not ascend."""
     K = int(getattr(d, "n_events", 0) if n_events is None else n_events)
     ev = d.carried["event"]
@@ -274,7 +275,8 @@ def split_dev(d, o, n_events=None):
     first = {k: h[i * (K + 1):(i + 1) * (K + 1)] for i, k in enumerate(("cand", "rem", "frag"))}
     names = [f for f, _ in nat.GtfExtractOutCounts._fields_]
     counts = [dict(zip(names, (int(x) for x in h[3 * (K + 1) + 6 * e:3 * (K + 1) + 6 * e + 6]))) for e in range(K)]
-    return {"first": first, "counts": counts, "cand_ptr_ev": pev}
+    return {"first": first, "counts": counts, "cand_ptr_ev": pev,
+            "cand_first_dev": small[:K + 1] if d.torch is not None else small.view(0, K + 1, small.dtype)}
 
 
 def candidate_order(g: TrackGraph) -> np.ndarray:

@@ -538,6 +538,273 @@ class DeviceScorer:
         return Result(n, self.tables.n_reference, tpur, ppur, rp, ng, matched)
 
 
+_OFFSET_FIELDS = ("node_off", "entry_off", "part_off")
+
+
+@dataclasses.dataclass
+class BatchTables:
+    """gtf_truth_batch's arrays on the host (include/gtf.h): K events' TruthTables end to end. Ids of
+    different events collide, so node_id and part_id ascend inside an event's segment only; node_ptr
+    holds every event's pointers shifted by its entry_off, and one closing entry."""
+    node_id: np.ndarray      # [sum T] int64
+    node_ptr: np.ndarray     # [sum T + 1] int32
+    node_part: np.ndarray    # [sum P] int64
+    part_id: np.ndarray      # [sum R] int64
+    part_hits: np.ndarray    # [sum R] int32
+    part_ref: np.ndarray     # [sum R] uint8
+    node_off: np.ndarray     # [K + 1] int32
+    entry_off: np.ndarray    # [K + 1] int32
+    part_off: np.ndarray     # [K + 1] int32
+    scored: np.ndarray       # [K] uint8: 0 = an event without truth
+    n_reference: list        # per event; None where it is not scored
+
+    def event(self, e: int) -> Optional[TruthTables]:
+        """event e's own tables again (None for an unscored event)"""
+        if not self.scored[e]:
+            return None
+        n0, n1, e0 = int(self.node_off[e]), int(self.node_off[e + 1]), int(self.entry_off[e])
+        p0, p1 = int(self.part_off[e]), int(self.part_off[e + 1])
+        return TruthTables(self.node_id[n0:n1], (self.node_ptr[n0:n1 + 1] - e0).astype(np.int32),
+                           self.node_part[e0:int(self.entry_off[e + 1])], self.part_id[p0:p1], self.part_hits[p0:p1],
+                           self.part_ref[p0:p1], self.n_reference[e])
+
+
+def _offsets(sizes) -> np.ndarray:
+    off = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(sizes, out=off[1:])
+    if off[-1] >= 1 << 31:
+        raise ValueError("the tables sum to 2^31 or more nodes, entries or particles")
+    return off.astype(np.int32)
+
+
+def concat_tables(tables) -> BatchTables:
+    """The host definition of gtf_truth_concat: the TruthTables of K events (None = an event without
+    truth: empty tables, scored 0) laid end to end."""
+    tables = list(tables)
+    live = [t for t in tables if t is not None]
+
+    def cat(name, dt):
+        return np.concatenate([np.asarray(getattr(t, name), dt) for t in live]) if live else np.zeros(0, dt)
+
+    size = lambda t, name: 0 if t is None else int(getattr(t, name).size)   # noqa: E731
+    node_off, entry_off, part_off = (_offsets([size(t, name) for t in tables]) for name in ("node_id", "node_part", "part_id"))
+    shift = [e for t, e in zip(tables, entry_off[:-1]) if t is not None]
+    ptr = [np.asarray(t.node_ptr, np.int64)[:-1] + int(e) for t, e in zip(live, shift)] + [np.array([entry_off[-1]], np.int64)]
+    return BatchTables(cat("node_id", np.int64), np.concatenate(ptr).astype(np.int32), cat("node_part", np.int64),
+                       cat("part_id", np.int64), cat("part_hits", np.int32), cat("part_ref", np.uint8), node_off,
+                       entry_off, part_off, np.array([t is not None for t in tables], np.uint8),
+                       [None if t is None else int(t.n_reference) for t in tables])
+
+
+class DeviceTruthBatch:
+    """truth_concat_dev's result: the arrays of BatchTables on the device and the GtfTruthBatch struct
+    gtf_score_candidates_ev takes. host() downloads them as a BatchTables."""
+
+    def __init__(self, mem: _Mem, arrays, batch, scored, n_reference, keep):
+        self._m, self.batch, self.device, self.mem = mem, batch, mem.device, mem.mem
+        self.n_events, self.n_nodes = int(batch.n_events), int(batch.n_nodes)
+        self.n_entries, self.n_particles = int(batch.n_entries), int(batch.n_particles)
+        self.scored, self.n_reference = scored, n_reference
+        self._buffers, self._keep = arrays, keep      # (the views point into them; the parts until the copy has run)
+        K = self.n_events
+        sizes = (self.n_nodes, self.n_nodes + 1, self.n_entries, self.n_particles, self.n_particles, self.n_particles,
+                 K + 1, K + 1, K + 1)
+        for name, a, n in zip([f for f, _ in _TABLE_FIELDS] + list(_OFFSET_FIELDS), arrays, sizes):
+            setattr(self, name, mem.first(a, n))
+
+    def host(self) -> BatchTables:
+        """the tables as concat_tables returns them (synchronises)"""
+        fields = list(_TABLE_FIELDS) + [(f, np.int32) for f in _OFFSET_FIELDS]
+        return BatchTables(*(self._m.host(getattr(self, name), getattr(self, name).numel(), dt) for name, dt in fields),
+                           self.scored.copy(), list(self.n_reference))
+
+
+def truth_concat_dev(tables, device="cuda", mem: str = "torch") -> DeviceTruthBatch:
+    """concat_tables on the device (gtf_truth_concat, csrc/gtf_score_ev.hip): two launches whatever the
+    number of events, nothing synchronises. Entries may be TruthTables (uploaded), DeviceTruth
+    (truth_tables_dev: used where it is) or None (an event without truth). One allocator and one device:
+    that of the DeviceTruth entries, which must agree, else ``device`` / ``mem``."""
+    from . import _native as nat
+    tables = list(tables)
+    on_dev = [t for t in tables if isinstance(t, DeviceTruth)]
+    mm = on_dev[0]._m if on_dev else _Mem(device, mem)
+    if any((t.mem, str(t.device)) != (mm.mem, str(mm.device)) for t in on_dev):
+        raise ValueError("truth_concat_dev: the DeviceTruth entries must share one allocator and one device")
+    K = len(tables)
+    sizes, parts, keep = (nat.GtfTruthSizes * max(K, 1))(), (nat.GtfTruthPart * max(K, 1))(), []
+    names = [f for f, _ in _TABLE_FIELDS]
+    for i, t in enumerate(tables):
+        if t is None:
+            continue
+        if isinstance(t, DeviceTruth):
+            arrays = [getattr(t, name) for name in names]
+            n = (t.n_nodes, t.n_entries, t.n_particles)
+        else:
+            arrays = [mm.from_host(np.ascontiguousarray(getattr(t, name), dt)) if np.size(getattr(t, name)) else None
+                      for name, dt in _TABLE_FIELDS]
+            n = (int(t.node_id.size), int(t.node_part.size), int(t.part_id.size))
+        keep.append(arrays)
+        sizes[i].n_nodes, sizes[i].n_entries, sizes[i].n_particles = n
+        parts[i].n_nodes, parts[i].n_entries, parts[i].n_particles = n
+        for name, a in zip(names, arrays):
+            setattr(parts[i], name, mm.p(a).value)
+    T, P, R = (sum(getattr(sizes[i], f) for i in range(K)) for f in ("n_nodes", "n_entries", "n_particles"))
+    if max(T, P, R) >= 1 << 31:
+        raise ValueError("the tables sum to 2^31 or more nodes, entries or particles")
+    out = [mm.empty(max(n, 1), dt) for (_, dt), n in zip(_TABLE_FIELDS, (T, T + 1, P, R, R, R))]
+    out += [mm.empty(K + 1, np.int32) for _ in _OFFSET_FIELDS]
+    scored = np.array([t is not None for t in tables], np.uint8)
+    d_scored = mm.from_host(scored) if K and not scored.all() else None
+    d_parts = mm.from_host(np.frombuffer(bytearray(parts), np.uint8)) if K else None
+    buf = nat.GtfTruthBatchBuf(*(mm.p(a) for a in out[6:] + out[:6]))
+    batch = nat.GtfTruthBatch(scored=mm.p(d_scored))
+    nb = int(mm.lib.gtf_truth_concat_workspace_bytes(K))
+    ws = mm.empty(nb, np.uint8)
+    nat.check(mm.lib.gtf_truth_concat(sizes, mm.p(d_parts), K, ctypes.byref(buf), ctypes.byref(batch), mm.p(ws),
+                                      ctypes.c_size_t(nb), mm.stream))
+    keep += [d_parts, d_scored, ws]
+    return DeviceTruthBatch(mm, out, batch, scored, [None if t is None else int(t.n_reference) for t in tables], keep)
+
+
+class BatchScorer:
+    """DeviceScorer for the K events of a fused graph at once (gtf_score_*_ev, csrc/gtf_score_ev.hip): one
+    add() per iteration takes the fused graph's candidates as gtf_extract_outputs and gtf_event_split
+    left them -- the global cand_ptr / cand_ids and cand_first (extract.split_dev: "cand_first_dev") --
+    and results() returns one Result per event, equal to what DeviceScorer.result() gives for that event
+    alone (None for an event without truth). The number of launches does not depend on K; add() never
+    synchronises, results() synchronises once for the batch. ``tables``: a DeviceTruthBatch, or a sequence
+    of TruthTables / DeviceTruth / None that truth_concat_dev concatenates."""
+
+    def __init__(self, tables, device="cuda", mem: str = "torch"):
+        if not isinstance(tables, DeviceTruthBatch):
+            tables = truth_concat_dev(tables, device, mem)
+        m = tables._m
+        self._m, self.nat, self.tables, self.mem = m, m.nat, tables, m.mem
+        self.torch, self.device, self.lib = m.torch, m.device, m.lib
+        self.K, self.R, self.batch = tables.n_events, tables.n_particles, tables.batch
+        r1 = max(self.R, 1)
+        self._state = [m.empty(r1, np.uint64), m.empty(r1, np.int32), m.empty(r1, np.int32), m.empty(2, np.uint32)]
+        self.state = self.nat.GtfScoreStateEv(n_particles=self.R, **{k: m.p(a) for k, a in zip(
+            ("best_key", "best_good", "best_total", "error"), self._state)})
+        self.reset()
+
+    _p = staticmethod(_Mem.p)
+
+    @property
+    def stream(self):
+        return self._m.stream
+
+    def reset(self, events=None):
+        """forget every candidate scored so far; or, with ``events`` (K booleans), those of the marked
+        events alone -- the others keep their claims, and the error words stay (does not synchronise)"""
+        mask = None
+        if events is None:
+            self._per, self._all_per, self._keep = [], True, []
+        else:
+            ev = np.ascontiguousarray(np.asarray(events, bool).reshape(-1), np.uint8)
+            if ev.size != self.K:
+                raise ValueError("reset(events=...) takes one entry per event")
+            if not self.K:
+                return
+            mask = self._m.from_host(ev)
+            for rec in self._per:       # (the per-candidate lists of the marked events go with their claims)
+                rec["dead"] = rec["dead"] | ev.astype(bool)
+            self._keep.append(mask)
+        self.nat.check(self.lib.gtf_score_reset_ev(ctypes.byref(self.state), ctypes.byref(self.batch), self._p(mask),
+                                                   self.stream))
+
+    def add(self, cand_ptr_dev, cand_ids_dev, cand_first_dev, n_cand: int, group: int, per_candidate: bool = False,
+            n_members: Optional[int] = None):
+        """Score the n_cand candidates of all events: cand_ptr_dev [n_cand + 1] int32 and cand_ids_dev int64
+        (gtf_extract_out's form, not rebased), cand_first_dev [K + 1] int32 (candidate c belongs to the
+        event e with cand_first[e] <= c < cand_first[e + 1]), all device arrays. n_members as
+        DeviceScorer.add. Nothing synchronises."""
+        nat = self.nat
+        n_cand, group = int(n_cand), int(group)
+        if n_cand == 0:
+            if not per_candidate:
+                self._all_per = False
+            return
+        if not cand_ids_dev.numel():      # (candidates without a member: the library still wants an array)
+            cand_ids_dev = self._m.empty(1, np.int64)
+        cap = int(cand_ids_dev.numel()) if n_members is None else int(n_members)
+        nb = int(self.lib.gtf_score_ev_workspace_bytes(n_cand, cap, self.K))
+        ws = self._m.empty(nb, np.uint8)
+        out = nat.GtfScoreOut()
+        if per_candidate:
+            pid, good = self._m.empty(n_cand, np.int64), self._m.empty(n_cand, np.int32)
+            out = nat.GtfScoreOut(self._p(pid), self._p(good), None, None)
+            self._per.append({"group": group, "n": n_cand, "pid": pid, "good": good, "first": cand_first_dev,
+                              "dead": np.zeros(self.K, bool)})
+        else:
+            self._all_per = False
+        nat.check(self.lib.gtf_score_candidates_ev(ctypes.byref(self.batch), self._p(cand_ptr_dev),
+                                                   self._p(cand_ids_dev), self._p(cand_first_dev), n_cand, group,
+                                                   ctypes.byref(out), ctypes.byref(self.state), self._p(ws),
+                                                   ctypes.c_size_t(nb), self.stream))
+        if self.torch is None:
+            self._keep.append(ws)      # (until results() has synchronised)
+
+    def add_batch(self, cand_ptr_dev, cand_ids_dev, cand_first_dev, n_cand: int, group: int, n_members=None,
+                  active=None):
+        """what pipeline.run_batch calls once per iteration. ``active`` (the events that entered the
+        iteration with nodes) is not needed here: an event without nodes has no candidates."""
+        self.add(cand_ptr_dev, cand_ids_dev, cand_first_dev, n_cand, group, n_members=n_members)
+
+    def results(self):
+        """One Result per event (None where it has no truth) of everything added since the event's last
+        reset; synchronises once. The purities are formed here, in fp64, from the integer records.
+        reconstructed_pid / n_good / matched are filled when every add asked for per_candidate."""
+        nat, m, K = self.nat, self._m, self.K
+        r1 = max(self.R, 1)
+        key, pid = m.empty(r1, np.uint64), m.empty(r1, np.int64)
+        good, total, hits = (m.empty(r1, np.int32) for _ in range(3))
+        first = m.empty(K + 1, np.int32)
+        nb = int(self.lib.gtf_score_finish_ev_workspace_bytes(self.R, K))
+        ws = m.empty(nb, np.uint8)
+        n_rec, err = np.zeros(max(K, 1), np.int32), np.zeros(2, np.uint32)
+        rc = self.lib.gtf_score_finish_ev(ctypes.byref(self.batch), ctypes.byref(self.state), self._p(key), self._p(pid),
+                                          self._p(good), self._p(total), self._p(hits), self._p(first),
+                                          ctypes.c_void_p(n_rec.ctypes.data), ctypes.c_void_p(err.ctypes.data),
+                                          self._p(ws), ctypes.c_size_t(nb), self.stream)
+        self._keep = []
+        if rc == -2 and err[0] & nat.SCORE_ERR_MISSING:
+            where = "event %d: " % int(err[1]) if int(err[1]) < K else ""
+            raise ValueError(where + "a candidate node has no hit_dissociation")
+        nat.check(rc)
+        at = np.zeros(K + 1, np.int64)
+        np.cumsum(n_rec[:K], out=at[1:])
+        n = int(at[-1])
+        g, t, h = (m.host(a, n, np.int32) for a in (good, total, hits))
+        per = None
+        if self._all_per and self._per:
+            k = m.host(key, n, np.uint64)
+            per = [dict(rec, first=m.host(rec["first"], K + 1, np.int32), pid=m.host(rec["pid"], rec["n"], np.int64),
+                        good=m.host(rec["good"], rec["n"], np.int32)) for rec in sorted(self._per, key=lambda x: x["group"])]
+        out = []
+        for e in range(K):
+            if not self.tables.scored[e]:
+                out.append(None)
+                continue
+            a, b = int(at[e]), int(at[e + 1])
+            ge = g[a:b] * 1.0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                tpur, ppur = ge / t[a:b], ge / h[a:b]
+            rp, ng, matched = np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, bool)
+            mine = [rec for rec in per if not rec["dead"][e]] if per is not None else []
+            if mine:
+                start, n_all = {}, 0
+                for rec in mine:
+                    start[rec["group"]] = n_all
+                    n_all += int(rec["first"][e + 1]) - int(rec["first"][e])
+                rp = np.concatenate([rec["pid"][rec["first"][e]:rec["first"][e + 1]] for rec in mine])
+                ng = np.concatenate([rec["good"][rec["first"][e]:rec["first"][e + 1]] for rec in mine]).astype(np.int64)
+                matched = np.zeros(n_all, bool)
+                matched[[start[int(x >> np.uint64(32))] + int(x & np.uint64(0xffffffff)) for x in k[a:b]]] = True
+            out.append(Result(b - a, self.tables.n_reference[e], tpur, ppur, rp, ng, matched))
+        return out
+
+
 def summary(r: Result) -> Dict[str, object]:
     return {"reconstructed": r.n_reconstructed, "reference": r.n_reference, "efficiency_pct": r.efficiency_str,
             "mean_track_purity": float(np.mean(r.track_purities)) if r.track_purities.size else None,

@@ -220,7 +220,10 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
     to run()'s on that event alone: the same records, and as many -- an event's list ends at the first
     iteration it enters with no node left, as run() breaks. ``seconds`` are the batch's.
     scorers: None, or one metrics.DeviceScorer (or None) per event; scorers[e] receives event e's
-    candidates of every iteration, group = (first + iterations - 1) - it as in run(). lists=False: no
+    candidates of every iteration, group = (first + iterations - 1) - it as in run(); or ONE object with
+    an add_batch method (metrics.BatchScorer), which gets one call per iteration for the whole batch:
+    add_batch(cand_ptr, cand_ids, cand_first_dev, n_extracted, group, n_members=..., active=[the events
+    that entered the iteration with nodes]) on the fused graph's own device arrays. lists=False: no
     node-id list crosses to the host. The input graphs are not modified.
     keep_graphs: every record also holds the event's stage output, remaining graph and remaining vivl
     (what run_pipeline.py saves), cut on the host (graph.split_events) from downloads of the fused
@@ -240,6 +243,9 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
         raise ValueError("run_batch takes a list of resident events or one fused graph of build_events_dev")
     ds = [fused] if fused is not None else list(ds)
     K = fused.n_events if fused is not None else len(ds)
+    batch_scorer = scorers if hasattr(scorers, "add_batch") else None
+    if batch_scorer is not None:
+        scorers = None
     if scorers is not None and len(scorers) != K:
         raise ValueError("scorers must hold one entry (a DeviceScorer or None) per event")
     for g in ds:
@@ -286,6 +292,10 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
         o = extract.outputs_dev(d, res, ex.numhits, ids=True, lists=False, members=True)
         sp = extract.split_dev(d, o, K)
         fc, fr, ff = (sp["first"][k] for k in ("cand", "rem", "frag"))
+        if batch_scorer is not None:   # one call for the batch: the fused graph's own arrays
+            batch_scorer.add_batch(o["cand_ptr"], o["cand_ids"], sp["cand_first_dev"], o["counts"]["n_extracted"],
+                                   last - it, n_members=o["counts"]["n_extracted_nodes"],
+                                   active=[left[e] > 0 for e in range(K)])
         if scorers is not None:
             at = 0   # event e's members start where the events before it end
             for e in range(K):

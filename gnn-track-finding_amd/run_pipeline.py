@@ -38,6 +38,10 @@ stops; the message does not say which event.
 --batch-build (with --batch) builds the events in ONE call (pipeline.build_events_dev:
 gtf_build_events_csr_device on the concatenated columns) instead of once per event followed by the concat:
 the same files under ROOTDIR/<i>/.
+--batch-metrics (with --batch and --truth) scores the whole batch with ONE pair of scorers
+(gtf.metrics.BatchScorer: gtf_score_candidates_ev once per iteration on the fused graph's candidates) instead
+of a pair per event; the truth tables are still made per event and then concatenated. The same metrics.json
+under every ROOTDIR/<i>/, byte for byte.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -82,8 +86,36 @@ def _parser_line(key, info):
     print("parse %s: %s%s" % (key, info[key], " (%s)" % info[key + "_reason"] if key + "_reason" in info else ""))
 
 
+class _BatchScorers:
+    """_Scorers for a whole batch (--batch-metrics): what pipeline.run_batch(scorers=...) feeds once per
+    iteration; the last-iteration scorer resets the events that entered the iteration with nodes"""
+
+    def __init__(self, tables, device):
+        from gtf import metrics
+        batch = metrics.truth_concat_dev(tables, device)
+        self.cumulative = metrics.BatchScorer(batch)
+        self.last = metrics.BatchScorer(batch)
+
+    def add_batch(self, cand_ptr, cand_ids, cand_first, n_cand, group, n_members=None, active=None):
+        self.cumulative.add_batch(cand_ptr, cand_ids, cand_first, n_cand, group, n_members=n_members, active=active)
+        self.last.reset(events=active)
+        self.last.add_batch(cand_ptr, cand_ids, cand_first, n_cand, 0, n_members=n_members, active=active)
+
+    def per_event(self):
+        """-> per event an object with _Scorers' two members, each holding its finished Result"""
+        import types
+        done = lambda r: types.SimpleNamespace(result=lambda: r)   # noqa: E731
+        return [None if c is None else types.SimpleNamespace(cumulative=done(c), last=done(l))
+                for c, l in zip(self.cumulative.results(), self.last.results())]
+
+
 def _scorers(args, truth_dir=None):
     """the truth files as reconstruction_efficiency.score reads them -> the two device scorers"""
+    return _Scorers(_tables(args, truth_dir), args.device)
+
+
+def _tables(args, truth_dir=None):
+    """the truth files as reconstruction_efficiency.score reads them -> the scorer's truth tables"""
     import numpy as np
     from gtf import metrics
     pre = os.path.join(truth_dir or args.truth, "event000001000-")
@@ -92,7 +124,7 @@ def _scorers(args, truth_dir=None):
         for key in ("particles", "mapping", "truth"):
             if key in info:
                 _parser_line(key, info)
-        return _Scorers(tables, args.device)
+        return tables
     import pandas as pd
     particles = pd.read_csv(pre + "particles.csv")
     m = metrics.HitMapping.from_frame(pd.read_csv(pre + args.mapping))
@@ -106,7 +138,7 @@ def _scorers(args, truth_dir=None):
         tables = metrics.truth_tables_dev(*cols, device=args.device)
     else:
         tables = metrics.truth_tables(*cols)
-    return _Scorers(tables, args.device)
+    return tables
 
 
 def main(argv=None):
@@ -150,6 +182,9 @@ def main(argv=None):
     ap.add_argument("--batch-build", action="store_true",
                     help="with --batch: one graph build for all events (pipeline.build_events_dev) instead of one "
                          "per event and a concat; the same files")
+    ap.add_argument("--batch-metrics", action="store_true",
+                    help="with --batch and --truth: one pair of scorers for the whole batch (gtf.metrics.BatchScorer: "
+                         "one scoring call per iteration) instead of a pair per event; the same metrics.json files")
     ap.add_argument("--truth", nargs="+", metavar="DIR",
                     help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py); with --batch one "
                          "directory for every event, or one per event")
@@ -168,6 +203,8 @@ def main(argv=None):
             ap.error("--batch names the event directories itself: not with -n")
     if args.batch_build and not args.batch:
         ap.error("--batch-build builds the events of --batch")
+    if args.batch_metrics and not (args.batch and args.truth_dirs):
+        ap.error("--batch-metrics scores the events of --batch against --truth")
     if args.resident_parse:
         args.resident_event = True
     if args.resident_event and args.start != 1:
@@ -300,9 +337,14 @@ def _batch(args, p, ex):
     truth = [None] * len(args.batch)
     if args.truth_dirs:
         truth = args.truth_dirs if len(args.truth_dirs) > 1 else args.truth_dirs * len(args.batch)
-    scorers = [_scorers(args, t) if t else None for t in truth]
-    its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=scorers if args.truth_dirs else None,
-                             first=1, keep_graphs=True)
+    if args.batch_metrics:   # one pair of scorers for the batch; the tables are still made per event
+        batch = _BatchScorers([_tables(args, t) if t else None for t in truth], args.device)
+        its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=batch, first=1, keep_graphs=True)
+        scorers = batch.per_event()
+    else:
+        scorers = [_scorers(args, t) if t else None for t in truth]
+        its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=scorers if args.truth_dirs else None,
+                                 first=1, keep_graphs=True)
     for i, rec in enumerate(its):
         root = os.path.join(args.outputDir, str(i))
         print("event %d:" % i)

@@ -33,6 +33,8 @@
  *   gtf_score_reset, gtf_score_candidates, gtf_score_finish
  *                    -> src/extract/reconstruction_efficiency.py:118-183 (the candidates'
  *                       majority particles, the three tests, the match order and its counts)
+ *   gtf_truth_concat, gtf_score_reset_ev, gtf_score_candidates_ev, gtf_score_finish_ev
+ *                    -> the same lines for the K events of a fused graph in one call
  *   gtf_truth_build  -> src/extract/reconstruction_efficiency.py:41-91 (the reference tracks) and
  *                       utilities/helper.py:466-479 (hit_dissociation): the scorer's static tables
  *   gtf_csv_parse    -> the pd.read_csv / np.loadtxt calls in front of both
@@ -811,6 +813,150 @@ int gtf_score_finish(const gtf_truth* truth, const gtf_score_state* state, uint6
                      int64_t* out_pid, int32_t* out_good, int32_t* out_total, int32_t* out_hits,
                      gtf_score_counts* counts, void* workspace, size_t workspace_bytes,
                      gtf_stream_t stream);
+
+/* ---- Scoring a batch of events in one call: gtf_score_candidates_ev ------------------
+ * reconstruction_efficiency.py:118-183 for the K events of a fused graph (gtf_graph_concat,
+ * gtf_build_events_csr_device) at once: what K gtf_score_candidates / gtf_score_finish calls
+ * compute, in launch sequences whose length does not depend on K. Node ids and particle ids of
+ * different events collide (the same event twice is the plain case), so the K truth tables are
+ * not merged: they lie end to end and every lookup stays inside its own event's segment, as
+ * gtf_candidate_order_device_ev looks node ids up. gtf_score_ev.hip.
+ *
+ * gtf_truth_batch: the K gtf_truth tables end to end, DEVICE arrays. node_id and part_id
+ * ascend inside an event's segment only; node_ptr holds every event's pointers shifted by its
+ * entry_off, and one closing entry. scored [K]: 0 = an event without truth, whose candidates are
+ * not looked up, claim nothing, raise no GTF_SCORE_ERR_MISSING and get 0 / 0 / 0 / 0 in the
+ * per-candidate outputs; NULL = every event is scored. */
+typedef struct gtf_truth_batch {
+    uint32_t struct_size;       /* sizeof(gtf_truth_batch) as the caller compiled it */
+    uint32_t abi_version;       /* GTF_ABI_VERSION */
+    int32_t n_events;           /* K */
+    int32_t n_nodes;            /* sum of T, < 2^31 */
+    int32_t n_entries;          /* sum of P, < 2^31 */
+    int32_t n_particles;        /* sum of R, < 2^31 */
+    const int32_t* node_off;    /* [K+1] event e's rows of node_id: node_off[e] .. node_off[e+1] */
+    const int32_t* entry_off;   /* [K+1] ... of node_part */
+    const int32_t* part_off;    /* [K+1] ... of part_id, part_hits, part_ref */
+    const int64_t* node_id;     /* [sum T] */
+    const int32_t* node_ptr;    /* [sum T + 1] */
+    const int64_t* node_part;   /* [sum P] */
+    const int64_t* part_id;     /* [sum R] */
+    const int32_t* part_hits;   /* [sum R] */
+    const uint8_t* part_ref;    /* [sum R] */
+    const uint8_t* scored;      /* [K] or NULL */
+} gtf_truth_batch;
+
+/* One part of gtf_truth_concat: the sizes on the HOST (checked and summed before any launch) ... */
+typedef struct gtf_truth_sizes {
+    int32_t n_nodes, n_entries, n_particles, pad_;
+} gtf_truth_sizes;
+
+/* ... and the same sizes beside the part's arrays in a DEVICE table. A part of size 0 may hold
+ * NULL arrays. */
+typedef struct gtf_truth_part {
+    int32_t n_nodes, n_entries, n_particles, pad_;
+    const int64_t* node_id;
+    const int32_t* node_ptr;
+    const int64_t* node_part;
+    const int64_t* part_id;
+    const int32_t* part_hits;
+    const uint8_t* part_ref;
+} gtf_truth_part;
+
+/* The caller-owned DEVICE arrays gtf_truth_concat fills, at the sizes of gtf_truth_batch. */
+typedef struct gtf_truth_batch_buf {
+    int32_t *node_off, *entry_off, *part_off;   /* each [K+1] */
+    int64_t* node_id;
+    int32_t* node_ptr;
+    int64_t* node_part;
+    int64_t* part_id;
+    int32_t* part_hits;
+    uint8_t* part_ref;
+} gtf_truth_batch_buf;
+
+/* Scratch of gtf_truth_concat: one word, set when the device table disagrees with the host's
+ * sizes (rows are then left unwritten); positive for 0 parts. */
+size_t gtf_truth_concat_workspace_bytes(int32_t n_parts);
+
+/* gtf/metrics.py concat_tables on the device, with gtf_graph_concat's conventions: sizes
+ * [n_parts] on the host, parts [n_parts] on the device. One block computes the three offset
+ * arrays; one launch over nodes, entries and particles copies every row, a thread finding its
+ * part by a binary search over the offsets (staged in LDS up to 2,048), node_ptr shifted by the
+ * part's entry_off; every write is clamped to the host's sums. Two launches whatever n_parts
+ * is; nothing synchronises, nothing is allocated. *out arrives with struct_size / abi_version
+ * set and `scored` as the caller wants it, and leaves with the counts and buf's pointers.
+ * Parts with T = 0, P = 0 or R = 0 are legal anywhere, and so is n_parts == 0. -3 for another
+ * ABI of *out; -2 for a null argument or array that is needed, negative sizes, a sum of 2^31
+ * or more, or a workspace below gtf_truth_concat_workspace_bytes: all before any launch. */
+int gtf_truth_concat(const gtf_truth_sizes* sizes, const gtf_truth_part* parts, int32_t n_parts,
+                     const gtf_truth_batch_buf* buf, gtf_truth_batch* out, void* workspace,
+                     size_t workspace_bytes, gtf_stream_t stream);
+
+/* gtf_score_state_ev: gtf_score_state for the whole batch, DEVICE arrays owned by the caller.
+ * Event e's words are those of its own gtf_score_state, at part_off[e] on. */
+typedef struct gtf_score_state_ev {
+    uint32_t struct_size;       /* sizeof(gtf_score_state_ev) as the caller compiled it */
+    uint32_t abi_version;       /* GTF_ABI_VERSION */
+    int32_t n_particles;        /* sum of R of the gtf_truth_batch it is used with */
+    int32_t pad_;
+    uint64_t* best_key;         /* [sum R] (group << 32) | candidate index INSIDE ITS EVENT; all-ones = none */
+    int32_t* best_good;         /* [sum R] */
+    int32_t* best_total;        /* [sum R] */
+    uint32_t* error;            /* [2] GTF_SCORE_ERR_* of all events; the smallest event index that set one
+                                   (an atomic minimum that runs only on a violation), INT32_MAX = none */
+} gtf_score_state_ev;
+
+/* reconstruction_efficiency.py:118-121 per event. events == NULL: every key all-ones, the error
+ * words cleared (0, INT32_MAX). Otherwise events is a DEVICE byte mask [K]: the keys of the
+ * marked events alone are reset and the error words stay -- the reset of a scorer that holds
+ * each event's latest iteration, where an event that has run out of nodes keeps its claims.
+ * One launch, no synchronisation. -3 / -2 as gtf_score_candidates_ev. */
+int gtf_score_reset_ev(const gtf_score_state_ev* state, const gtf_truth_batch* batch,
+                       const uint8_t* events, gtf_stream_t stream);
+
+/* Scratch of one gtf_score_candidates_ev call: as gtf_score_workspace_bytes, and one word per
+ * candidate more (its event). Does not depend on n_events. */
+size_t gtf_score_ev_workspace_bytes(int32_t n_cand, int32_t n_members, int32_t n_events);
+
+/* gtf_score_candidates (reconstruction_efficiency.py:125-163) for the candidates of K events in
+ * the form gtf_extract_outputs and gtf_event_split leave them for the fused graph: the global
+ * cand_ptr [n_cand + 1] and cand_ids, not rebased, and cand_first [K + 1] (device): candidate c
+ * belongs to the event e with cand_first[e] <= c < cand_first[e + 1], and so do its members.
+ *   A small first launch finds every candidate's event (an upper bound over cand_first, staged
+ * in LDS up to 2,048 entries) and checks cand_first; then the three launches and the exclusive
+ * sum of gtf_score_candidates: a member is searched in node_id[node_off[e] .. node_off[e + 1]),
+ * the vote is the same (16 lanes, the wavefront, the chunked loop), the particle is searched in
+ * part_id[part_off[e] .. part_off[e + 1]) and claimed by a 64-bit atomic minimum on
+ * best_key[part_off[e] + r] with the key (group << 32) | (c - cand_first[e]). After any sequence
+ * of calls best_key, best_good and best_total are the K states of gtf_score_candidates laid end
+ * to end, word for word, and the per-candidate outputs [n_cand] the K outputs concatenated.
+ *   Nothing is allocated, nothing synchronises, no atomic on a shared word except on a
+ * violation, every read is clamped to the batch's sums. cand_first[0] != 0, a decreasing
+ * cand_first or cand_first[K] != n_cand set GTF_SCORE_ERR_RANGE and the candidates whose event
+ * they leave open are skipped as those of an unscored event. More members than the workspace
+ * holds: GTF_SCORE_ERR_WORKSPACE. n_cand == 0: returns 0, nothing launched. -3 for another ABI
+ * of *batch or *state; -2 as gtf_score_candidates, before any launch. */
+int gtf_score_candidates_ev(const gtf_truth_batch* batch, const int32_t* cand_ptr,
+                            const int64_t* cand_ids, const int32_t* cand_first, int32_t n_cand,
+                            int32_t group, const gtf_score_out* out, const gtf_score_state_ev* state,
+                            void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* Scratch of gtf_score_finish_ev for sum R particles of K events: positive for 0, non-decreasing. */
+size_t gtf_score_finish_ev_workspace_bytes(int32_t n_particles, int32_t n_events);
+
+/* gtf_score_finish (reconstruction_efficiency.py:166-171, :213) per event: one hipCUB segmented
+ * radix sort of the keys over part_off (which must be what gtf_truth_concat wrote), one count
+ * per event, one exclusive sum, one launch that writes the records compacted: event e's at
+ * rec_first[e] .. rec_first[e + 1] (rec_first: DEVICE [K + 1]), ascending by key inside the
+ * event. out_*: DEVICE arrays [sum R], NULL = not wanted. n_reconstructed [K] and error [2] are
+ * HOST arrays, filled by the call's one synchronisation. Errors return -2 with
+ * gtf_score_finish's messages, led by the event of error[1] where there is one: "event 3: a
+ * candidate node has no hit_dissociation". */
+int gtf_score_finish_ev(const gtf_truth_batch* batch, const gtf_score_state_ev* state,
+                        uint64_t* out_key, int64_t* out_pid, int32_t* out_good, int32_t* out_total,
+                        int32_t* out_hits, int32_t* rec_first, int32_t* n_reconstructed,
+                        uint32_t* error, void* workspace, size_t workspace_bytes,
+                        gtf_stream_t stream);
 
 /* ---- The truth tables themselves: gtf_truth_build ---------------------------------
  * gtf/metrics.py truth_tables (reconstruction_efficiency.py:41-91, helper.py:466-479) on the
