@@ -230,6 +230,22 @@ class GtfTruthCounts(ctypes.Structure):
                 ("error", U32), ("pad_", I32)]
 
 
+class GtfTruthInEv(ctypes.Structure):
+    """gtf_truth_in_ev: the parsed columns of K events end to end that gtf_truth_build_ev reads: three
+    HOST offset arrays [K + 1] and eleven device columns; keyword construction only -- struct_size /
+    abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_events", I32), ("num_layers", I32),
+                ("min_volume", I32), ("max_volume", I32), ("pt_cut", F64), ("row_off", P), ("truth_off", P),
+                ("particle_off", P), ("node_idx", P), ("hit_id", P), ("particle_id", P), ("volume_id", P),
+                ("layer_id", P), ("module_id", P), ("truth_hit", P), ("truth_part", P), ("part_id", P),
+                ("px", P), ("py", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfTruthInEv)
+        self.abi_version = ABI_VERSION
+
+
 TRUTH_ERR_MISSING, TRUTH_ERR_RANGE = 1, 2   # GTF_TRUTH_ERR_*
 TRUTH_ID_LIMIT = 1 << 21                    # volume_id, layer_id, module_id: [0, 2^21)
 
@@ -446,6 +462,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_score_ev_workspace_bytes", "gtf_score_candidates_ev",
            "gtf_score_finish_ev_workspace_bytes", "gtf_score_finish_ev",
            "gtf_truth_build_workspace_bytes", "gtf_truth_build",
+           "gtf_truth_build_ev_workspace_bytes", "gtf_truth_build_ev",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_build_events_device_workspace_bytes", "gtf_build_events_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
@@ -563,7 +580,11 @@ def lib(lean: bool = False):
     L.gtf_truth_build_workspace_bytes.argtypes = [I32, I32, I32]
     L.gtf_truth_build.argtypes = [ctypes.POINTER(GtfTruthIn), ctypes.POINTER(GtfTruthBuf), TR,
                                   ctypes.POINTER(GtfTruthCounts), P, ctypes.c_size_t, P]
-    SH = ctypes.POINTER(GtfShard)
+    L.gtf_truth_build_ev_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_truth_build_ev_workspace_bytes.argtypes = [I32, I32, I32, I32]
+    L.gtf_truth_build_ev.argtypes = [ctypes.POINTER(GtfTruthInEv), ctypes.POINTER(GtfTruthBatchBuf), TB,
+                                     ctypes.POINTER(GtfTruthCounts), P, ctypes.c_size_t, P]
+    SH =ctypes.POINTER(GtfShard)
     L.gtf_pass_shard.argtypes = [G, N, S, S, E, PR, SH, P, P, ctypes.POINTER(P)]
     L.gtf_tag_sweep_shard.argtypes = [G, P, P, P, P, SH, I32, I32, P]
     L.gtf_shard_chunk_bytes.restype = ctypes.c_size_t
@@ -648,7 +669,7 @@ def lib(lean: bool = False):
                "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
                "gtf_event_split", "gtf_build_events_csr_device", "gtf_truth_concat", "gtf_score_reset_ev",
-               "gtf_score_candidates_ev", "gtf_score_finish_ev"):
+               "gtf_score_candidates_ev", "gtf_score_finish_ev", "gtf_truth_build_ev"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

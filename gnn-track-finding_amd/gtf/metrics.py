@@ -29,6 +29,8 @@ iteration, against the event's static tables (:func:`truth_tables`) uploaded onc
 gtf_score_finish returns the matched particles in match order; no candidate list crosses
 to the host. :func:`truth_tables_dev` builds those tables on the device as well
 (gtf_truth_build, csrc/gtf_truth.hip), from the columns uploaded once: the same arrays.
+For a batch of events :func:`truth_tables_batch_dev` builds the tables of all of them in one call
+(gtf_truth_build_ev, csrc/gtf_truth_ev.hip): what truth_concat_dev of the per-event tables leaves.
 """
 from __future__ import annotations
 
@@ -379,15 +381,11 @@ def truth_tables_dev(m: HitMapping, particle_id, px, py, min_volume: int, max_vo
 MAPPING_COLUMNS = ("node_idx", "hit_id", "particle_id", "volume_id", "layer_id", "module_id")
 
 
-def truth_files_dev(prefix: str, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch"):
-    """truth_tables_dev from the files reconstruction_efficiency.score reads (``prefix`` +
-    "particles.csv", + ``mapping``, and + "truth.csv" where it exists), each parsed on the device
-    (gtf.csvdev.parse_dev) with its columns chosen by header name, whatever else the file holds. A
-    file with a field outside the parser's exact domain is read with pd.read_csv instead. Returns
-    (DeviceTruth, {"particles" | "mapping" | "truth": "device" | "host"})."""
+def _read_truth_files(mm: _Mem, prefix: str, mapping: str):
+    """the columns of one event's truth files, as truth_files_dev documents them -> (HitMapping,
+    particle_id, px, py, truth hit_id or None, truth particle_id or None, info)"""
     import os
     from .csvdev import OutOfDomain, parse_dev
-    mm = _Mem(device, mem)
     info = {}
 
     def read(key, path, columns):
@@ -406,6 +404,16 @@ def truth_files_dev(prefix: str, mapping: str, min_volume: int, max_volume: int,
     th = tp = None
     if os.path.isfile(prefix + "truth.csv"):
         th, tp = read("truth", prefix + "truth.csv", (("hit_id", "int64"), ("particle_id", "int64")))
+    return m, pid, px, py, th, tp, info
+
+
+def truth_files_dev(prefix: str, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch"):
+    """truth_tables_dev from the files reconstruction_efficiency.score reads (``prefix`` +
+    "particles.csv", + ``mapping``, and + "truth.csv" where it exists), each parsed on the device
+    (gtf.csvdev.parse_dev) with its columns chosen by header name, whatever else the file holds. A
+    file with a field outside the parser's exact domain is read with pd.read_csv instead. Returns
+    (DeviceTruth, {"particles" | "mapping" | "truth": "device" | "host"})."""
+    m, pid, px, py, th, tp, info = _read_truth_files(_Mem(device, mem), prefix, mapping)
     return truth_tables_dev(m, pid, px, py, min_volume, max_volume, th, tp, device, mem), info
 
 
@@ -664,6 +672,169 @@ def truth_concat_dev(tables, device="cuda", mem: str = "torch") -> DeviceTruthBa
                                       ctypes.c_size_t(nb), mm.stream))
     keep += [d_parts, d_scored, ws]
     return DeviceTruthBatch(mm, out, batch, scored, [None if t is None else int(t.n_reference) for t in tables], keep)
+
+
+def truth_tables_batch(parts, min_volume: int, max_volume: int) -> BatchTables:
+    """The host definition of gtf_truth_build_ev: concat_tables of every event's truth_tables, one window
+    for the batch. A part is (HitMapping, particle_id, px, py, truth_hit_id=None, truth_particle_id=None),
+    or None for an event without truth (zero rows, scored 0)."""
+    return concat_tables([None if p is None else truth_tables(p[0], p[1], p[2], p[3], min_volume, max_volume,
+                                                              *tuple(p)[4:6]) for p in parts])
+
+
+_BATCH_DTYPES = (np.int64,) * 9 + (np.float64,) * 2   # six mapping columns, truth_hit / truth_part, part_id; px, py
+
+
+def _gather_dev(mm: _Mem, cols, dtypes, axes, n0, n1):
+    """device columns of K events end to end, as DeviceGraph._gather_columns gathers an event's: the offsets
+    of gtf_graph_concat with no structure output (two axes: sizes n0 and n1 per event) and
+    gtf_concat_columns. cols[i][e]: column i of event e (None where it has no rows), 8 bytes a row, on
+    axis axes[i]. No launch per event. -> one array per column (None for an empty axis)"""
+    nat, L, K, C = mm.nat, mm.lib, len(n0), len(cols)
+    total = (int(sum(n0)), int(sum(n1)))
+    adr = lambda t: t.data_ptr() if t is not None and t.numel() else 0  # noqa: E731
+    if any(adr(a) % 8 for c in cols for a in c):
+        raise ValueError("truth_tables_batch_dev: a device column is not aligned to 8 bytes")
+    dst = [mm.empty(total[ax], dt) if total[ax] else None for ax, dt in zip(axes, dtypes)]
+    ptab = (nat.GtfConcatPart * K)(*[nat.GtfConcatPart(n0[e], n1[e], 0, 0, 0, 0, 0, 0, 0) for e in range(K)])
+    pwords = ctypes.sizeof(nat.GtfConcatPart) // 8
+    host = np.zeros(K * (pwords + C), np.int64)
+    host[:K * pwords] = np.frombuffer(ptab, np.int64)
+    for i in range(C):
+        host[K * (pwords + i):K * (pwords + i + 1)] = [adr(cols[i][e]) if (n1 if axes[i] else n0)[e] else 0
+                                                       for e in range(K)]
+    tab = mm.from_host(host)
+    nb = int(L.gtf_graph_concat_workspace_bytes(K))
+    ws = mm.empty(nb, np.uint8)
+    hs = (nat.GtfConcatSizes * K)(*[nat.GtfConcatSizes(n0[e], n1[e], 0, 0) for e in range(K)])
+    nat.check(L.gtf_graph_concat(hs, ctypes.c_void_p(tab.data_ptr()), K, ctypes.byref(nat.GtfConcatOut()), mm.p(ws),
+                                 ctypes.c_size_t(nb), mm.stream))
+    cc = (nat.GtfConcatColumn * C)(*[nat.GtfConcatColumn(tab.data_ptr() + 8 * K * (pwords + i), mm.p(dst[i]), 8, axes[i])
+                                     for i in range(C)])
+    nat.check(L.gtf_concat_columns(mm.p(ws), K, total[0], total[1], cc, C, mm.stream))
+    # the table and the workspace go out of scope with kernels in flight: a torch allocation is reused in
+    # stream order, a plain one is freed at once
+    if mm.torch is None:
+        nat.check(L.gtf_stream_synchronize(None))
+    return dst
+
+
+def truth_tables_batch_dev(parts, min_volume: int, max_volume: int, device="cuda", mem: str = "torch") -> DeviceTruthBatch:
+    """truth_tables_batch on the device in ONE build (gtf_truth_build_ev, csrc/gtf_truth_ev.hip): what
+    truth_concat_dev([truth_tables_dev(...) for each part]) leaves, word for word, with one synchronisation
+    and a number of launches that does not depend on len(parts). The columns are all host arrays
+    (concatenated, and uploaded once per column: eleven uploads whatever K) or all device arrays of this
+    allocator (gathered by gtf_graph_concat's offsets and gtf_concat_columns, no launch per part); a mix
+    is a ValueError. The ValueErrors of truth_tables_dev carry over with the event in the text."""
+    return _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, lambda what: None)
+
+
+def _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, mark):
+    """truth_tables_batch_dev; mark("build") / mark("built") are called around the library call
+    (tools/batch_truth.py records device events there)"""
+    from . import _native as nat
+    parts = list(parts)
+    K = len(parts)
+    is_dev = lambda a: hasattr(a, "data_ptr")  # noqa: E731
+    size = lambda a: 0 if a is None else int(a.numel()) if is_dev(a) else int(a.size)  # noqa: E731
+    events = []      # per event its eleven columns (truth_hit / truth_part None: the mapping's own), or None
+    for e, p in enumerate(parts):
+        if p is None:
+            events.append(None)
+            continue
+        p = tuple(p)
+        if len(p) not in (4, 6):
+            raise ValueError("event %d: a part is (HitMapping, particle_id, px, py[, truth_hit_id, truth_particle_id]) "
+                             "or None" % e)
+        th, tp = p[4:6] if len(p) == 6 else (None, None)
+        if (th is None) != (tp is None):
+            raise ValueError("event %d: truth_hit_id and truth_particle_id come together" % e)
+        raw = [getattr(p[0], c) for c in MAPPING_COLUMNS] + [th, tp] + list(p[1:4])
+        cols = [a if a is None or is_dev(a) else np.ascontiguousarray(a, dt).reshape(-1) for a, dt in zip(raw, _BATCH_DTYPES)]
+        n = size(cols[0])
+        if any(size(c) != n for c in cols[:6]):
+            raise ValueError("event %d: mapping columns of different lengths" % e)
+        if th is not None:
+            if size(cols[6]) != size(cols[7]):
+                raise ValueError("event %d: truth columns of different lengths" % e)
+            if size(cols[6]) == 0:      # (for the library no truth rows means "the mapping's own columns")
+                if n:
+                    raise ValueError("event %d: a mapped hit has no truth row (helper.__get_particle_id .item())" % e)
+                cols[6] = cols[7] = None
+        if not size(cols[8]) == size(cols[9]) == size(cols[10]):
+            raise ValueError("event %d: particle columns of different lengths" % e)
+        events.append(cols)
+    on_dev = [is_dev(a) for cols in events if cols is not None for a in cols if a is not None]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("truth_tables_batch_dev: the columns are all host arrays or all device arrays")
+    if min_volume > max_volume:
+        raise ValueError("min_volume > max_volume")
+    sizes = [[0 if cols is None else size(cols[i]) for cols in events] for i in (0, 6, 8)]   # rows, truth rows, particles
+    offs = [np.concatenate([[0], np.cumsum(s, dtype=np.int64)]) for s in sizes]
+    if max(int(o[-1]) for o in offs) > 1 << 30:
+        raise ValueError("more than 2^30 rows")
+    row_off, truth_off, particle_off = (np.ascontiguousarray(o, np.int32) for o in offs)
+    N, NT, NP = int(row_off[-1]), int(truth_off[-1]), int(particle_off[-1])
+    mm = _Mem(device, mem)
+    per_column = [[None if cols is None else cols[i] for cols in events] for i in range(11)]
+    if not N:
+        dev = [None] * 11          # (nothing is read)
+    elif on_dev and on_dev[0] and K == 1:
+        dev = [a if size(a) else None for a in events[0]]      # (one event: its columns are the batch's)
+    elif on_dev and on_dev[0]:
+        dev = _gather_dev(mm, per_column[:8], _BATCH_DTYPES[:8], [0] * 6 + [1] * 2, sizes[0], sizes[1])
+        dev += _gather_dev(mm, per_column[8:], _BATCH_DTYPES[8:], [0] * 3, sizes[2], [0] * K) if NP else [None] * 3
+    else:
+        dev = [mm.from_host(np.concatenate([a for a in c if a is not None])) if total else None
+               for c, total in zip(per_column, [N] * 6 + [NT] * 2 + [NP] * 3)]
+    names = MAPPING_COLUMNS + ("truth_hit", "truth_part", "part_id", "px", "py")
+    tin = nat.GtfTruthInEv(n_events=K, num_layers=NUM_DISTINCT_LAYERS, min_volume=int(min_volume),
+                           max_volume=int(max_volume), pt_cut=PT_CUT, row_off=row_off.ctypes.data,
+                           truth_off=truth_off.ctypes.data, particle_off=particle_off.ctypes.data,
+                           **{k: mm.p(a) for k, a in zip(names, dev)})
+    out = [mm.empty(max(N, 1) + (name == "node_ptr"), dt) for name, dt in _TABLE_FIELDS]
+    out += [mm.empty(K + 1, np.int32) for _ in _OFFSET_FIELDS]
+    scored = np.array([p is not None for p in parts], np.uint8)
+    d_scored = mm.from_host(scored) if K and not scored.all() else None
+    buf = nat.GtfTruthBatchBuf(*(mm.p(a) for a in out[6:] + out[:6]))
+    batch = nat.GtfTruthBatch(scored=mm.p(d_scored))
+    nb = int(mm.lib.gtf_truth_build_ev_workspace_bytes(N, NT, NP, K))
+    ws = mm.empty(nb, np.uint8)
+    cnt = (nat.GtfTruthCounts * max(K, 1))()
+    mark("build")
+    rc = mm.lib.gtf_truth_build_ev(ctypes.byref(tin), ctypes.byref(buf), ctypes.byref(batch), cnt, mm.p(ws),
+                                   ctypes.c_size_t(nb), mm.stream)
+    mark("built")
+    if rc == -2:
+        for e in range(K):
+            if cnt[e].error & nat.TRUTH_ERR_RANGE:
+                raise ValueError("event %d: a volume_id, layer_id or module_id outside [0, %d): the device builder "
+                                 "packs them into one key (use metrics.truth_tables_batch)" % (e, nat.TRUTH_ID_LIMIT))
+            if cnt[e].error & nat.TRUTH_ERR_MISSING:
+                raise ValueError("event %d: a mapped hit has no truth row (helper.__get_particle_id .item())" % e)
+    nat.check(rc)
+    n_reference = [int(cnt[e].n_reference) if scored[e] else None for e in range(K)]
+    return DeviceTruthBatch(mm, out, batch, scored, n_reference, [d_scored, ws, dev])
+
+
+def truth_files_batch_dev(prefixes, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch"):
+    """truth_tables_batch_dev from the files of K events: each event's files are parsed as truth_files_dev
+    parses them (per file, on the device; a file outside the parser's exact domain is read with
+    pd.read_csv and uploaded), then ONE build makes the tables. ``prefixes``: one per event, or None for an
+    event without truth. Returns (DeviceTruthBatch, [truth_files_dev's info per event, None without truth])."""
+    mm = _Mem(device, mem)
+    parts, infos = [], []
+    for prefix in prefixes:
+        if prefix is None:
+            parts.append(None)
+            infos.append(None)
+            continue
+        m, pid, px, py, th, tp, info = _read_truth_files(mm, prefix, mapping)
+        cols = [a if a is None or hasattr(a, "data_ptr") else mm.from_host(a)
+                for a in [getattr(m, c) for c in MAPPING_COLUMNS] + [pid, px, py, th, tp]]
+        parts.append((HitMapping(*cols[:6]),) + tuple(cols[6:9]) + (() if th is None else tuple(cols[9:])))
+        infos.append(info)
+    return truth_tables_batch_dev(parts, min_volume, max_volume, device, mem), infos
 
 
 class BatchScorer:

@@ -42,6 +42,9 @@ the same files under ROOTDIR/<i>/.
 (gtf.metrics.BatchScorer: gtf_score_candidates_ev once per iteration on the fused graph's candidates) instead
 of a pair per event; the truth tables are still made per event and then concatenated. The same metrics.json
 under every ROOTDIR/<i>/, byte for byte.
+--batch-truth (with --batch-metrics) makes the truth tables of the whole batch in ONE build as well
+(gtf.metrics.truth_tables_batch_dev: gtf_truth_build_ev on the events' columns laid end to end; with
+--resident-parse the truth files are parsed on the GPU first, per file). The same metrics.json files.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -91,8 +94,9 @@ class _BatchScorers:
     iteration; the last-iteration scorer resets the events that entered the iteration with nodes"""
 
     def __init__(self, tables, device):
+        """tables: one entry per event (truth_concat_dev's), or the batch's DeviceTruthBatch (--batch-truth)"""
         from gtf import metrics
-        batch = metrics.truth_concat_dev(tables, device)
+        batch = tables if isinstance(tables, metrics.DeviceTruthBatch) else metrics.truth_concat_dev(tables, device)
         self.cumulative = metrics.BatchScorer(batch)
         self.last = metrics.BatchScorer(batch)
 
@@ -114,9 +118,47 @@ def _scorers(args, truth_dir=None):
     return _Scorers(_tables(args, truth_dir), args.device)
 
 
+def _truth_columns(args, pre):
+    """the truth files as reconstruction_efficiency.score reads them, by the host reader -> (HitMapping,
+    particle_id, px, py, truth hit_id or None, truth particle_id or None)"""
+    import numpy as np
+    import pandas as pd
+    from gtf import metrics
+    particles = pd.read_csv(pre + "particles.csv")
+    m = metrics.HitMapping.from_frame(pd.read_csv(pre + args.mapping))
+    th = tp = None
+    if os.path.isfile(pre + "truth.csv"):
+        truth = pd.read_csv(pre + "truth.csv", usecols=["hit_id", "particle_id"])
+        th, tp = truth.hit_id.to_numpy(np.int64), truth.particle_id.to_numpy(np.int64)
+    return m, particles.particle_id.to_numpy(), particles.px.to_numpy(), particles.py.to_numpy(), th, tp
+
+
+def _tables_batch(args, truth):
+    """--batch-truth: the truth tables of the whole batch from ONE build (gtf.metrics.truth_tables_batch_dev;
+    with --resident-parse the files are parsed on the GPU, per file: truth_files_batch_dev); truth: one
+    directory per event, None = an event without truth"""
+    from gtf import metrics
+    pres = [os.path.join(t, "event000001000-") if t else None for t in truth]
+    if args.resident_parse:
+        batch, infos = metrics.truth_files_batch_dev(pres, args.mapping, args.min_volume, args.max_volume, args.device)
+        for i, info in enumerate(infos):
+            for key in ("particles", "mapping", "truth"):
+                if info and key in info:
+                    print("event %d " % i, end="")
+                    _parser_line(key, info)
+        return batch
+    parts = []
+    for pre in pres:
+        if pre is None:
+            parts.append(None)
+            continue
+        m, pid, px, py, th, tp = _truth_columns(args, pre)
+        parts.append((m, pid, px, py) + ((th, tp) if th is not None else ()))
+    return metrics.truth_tables_batch_dev(parts, args.min_volume, args.max_volume, args.device)
+
+
 def _tables(args, truth_dir=None):
     """the truth files as reconstruction_efficiency.score reads them -> the scorer's truth tables"""
-    import numpy as np
     from gtf import metrics
     pre = os.path.join(truth_dir or args.truth, "event000001000-")
     if args.resident_parse and args.resident_truth:
@@ -125,15 +167,8 @@ def _tables(args, truth_dir=None):
             if key in info:
                 _parser_line(key, info)
         return tables
-    import pandas as pd
-    particles = pd.read_csv(pre + "particles.csv")
-    m = metrics.HitMapping.from_frame(pd.read_csv(pre + args.mapping))
-    th = tp = None
-    if os.path.isfile(pre + "truth.csv"):
-        truth = pd.read_csv(pre + "truth.csv", usecols=["hit_id", "particle_id"])
-        th, tp = truth.hit_id.to_numpy(np.int64), truth.particle_id.to_numpy(np.int64)
-    cols = (m, particles.particle_id.to_numpy(), particles.px.to_numpy(), particles.py.to_numpy(), args.min_volume,
-            args.max_volume, th, tp)
+    m, pid, px, py, th, tp = _truth_columns(args, pre)
+    cols = (m, pid, px, py, args.min_volume, args.max_volume, th, tp)
     if args.resident_truth:
         tables = metrics.truth_tables_dev(*cols, device=args.device)
     else:
@@ -185,6 +220,10 @@ def main(argv=None):
     ap.add_argument("--batch-metrics", action="store_true",
                     help="with --batch and --truth: one pair of scorers for the whole batch (gtf.metrics.BatchScorer: "
                          "one scoring call per iteration) instead of a pair per event; the same metrics.json files")
+    ap.add_argument("--batch-truth", action="store_true",
+                    help="with --batch-metrics: the truth tables of the whole batch come from one build "
+                         "(gtf.metrics.truth_tables_batch_dev) instead of one per event and a concat; the same "
+                         "metrics.json files")
     ap.add_argument("--truth", nargs="+", metavar="DIR",
                     help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py); with --batch one "
                          "directory for every event, or one per event")
@@ -205,6 +244,8 @@ def main(argv=None):
         ap.error("--batch-build builds the events of --batch")
     if args.batch_metrics and not (args.batch and args.truth_dirs):
         ap.error("--batch-metrics scores the events of --batch against --truth")
+    if args.batch_truth and not args.batch_metrics:
+        ap.error("--batch-truth builds the truth tables of --batch-metrics")
     if args.resident_parse:
         args.resident_event = True
     if args.resident_event and args.start != 1:
@@ -337,8 +378,11 @@ def _batch(args, p, ex):
     truth = [None] * len(args.batch)
     if args.truth_dirs:
         truth = args.truth_dirs if len(args.truth_dirs) > 1 else args.truth_dirs * len(args.batch)
-    if args.batch_metrics:   # one pair of scorers for the batch; the tables are still made per event
-        batch = _BatchScorers([_tables(args, t) if t else None for t in truth], args.device)
+    if args.batch_metrics:   # one pair of scorers for the batch; the tables per event, or (--batch-truth) in one build
+        if args.batch_truth:
+            batch = _BatchScorers(_tables_batch(args, truth), args.device)
+        else:
+            batch = _BatchScorers([_tables(args, t) if t else None for t in truth], args.device)
         its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=batch, first=1, keep_graphs=True)
         scorers = batch.per_event()
     else:

@@ -1043,6 +1043,76 @@ int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth*
                     gtf_truth_counts* counts, void* workspace, size_t workspace_bytes,
                     gtf_stream_t stream);
 
+/* ---- A batch's truth tables in one call: gtf_truth_build_ev ----------------------------
+ * gtf/metrics.py truth_tables_batch (reconstruction_efficiency.py:41-91, helper.py:466-479 per
+ * event) on the device: the parsed columns of K events laid end to end go in, and what comes
+ * out is the gtf_truth_batch that gtf_truth_concat of the K single gtf_truth_build results
+ * leaves, word for word. gtf_truth_ev.hip.
+ *
+ * One window and one cut per batch. Event e's mapping rows are row_off[e] .. row_off[e + 1]
+ * of the six mapping columns, its truth rows truth_off[e] .. truth_off[e + 1] of truth_hit /
+ * truth_part, its particles particle_off[e] .. particle_off[e + 1] of part_id / px / py. The
+ * three offset arrays are HOST arrays of n_events + 1 int32, start at 0 and do not decrease.
+ * An event with truth_off[e] == truth_off[e + 1] and rows uses its mapping's own hit_id /
+ * particle_id as truth columns (gtf_truth_in's n_truth == 0); both kinds may be mixed. The
+ * limits of gtf_truth_build hold for the sums. */
+typedef struct gtf_truth_in_ev {
+    uint32_t struct_size;        /* sizeof(gtf_truth_in_ev) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    int32_t n_events;            /* K */
+    int32_t num_layers;          /* as gtf_truth_in */
+    int32_t min_volume;
+    int32_t max_volume;
+    double pt_cut;
+    const int32_t* row_off;      /* HOST [K + 1] */
+    const int32_t* truth_off;    /* HOST [K + 1] */
+    const int32_t* particle_off; /* HOST [K + 1] */
+    const int64_t* node_idx;     /* DEVICE [row_off[K]] the six columns of the mappings */
+    const int64_t* hit_id;
+    const int64_t* particle_id;
+    const int64_t* volume_id;
+    const int64_t* layer_id;
+    const int64_t* module_id;
+    const int64_t* truth_hit;    /* DEVICE [truth_off[K]] or NULL when that is 0 */
+    const int64_t* truth_part;
+    const int64_t* part_id;      /* DEVICE [particle_off[K]] */
+    const double* px;
+    const double* py;
+} gtf_truth_in_ev;
+
+/* Scratch of gtf_truth_build_ev for the summed sizes: positive for zero sizes, non-decreasing in
+ * each argument (negative counts as 0). The truth tables are sized for n_rows + n_truth rows, so
+ * it does not depend on which events bring truth columns of their own. */
+size_t gtf_truth_build_ev_workspace_bytes(int32_t n_rows, int32_t n_truth, int32_t n_particles,
+                                          int32_t n_events);
+
+/* gtf_truth_build's five steps (reconstruction_efficiency.py:41-91, helper.py:466-479) on global
+ * indices. A first launch writes one int32 event column per axis (a binary search over the
+ * offsets, uploaded once in stream order). Ids of different events collide and cannot be
+ * shifted, so every sorted table is ordered by (event, key): the 64-bit key sort, then one
+ * stable radix pass over the bits K needs on the event word (skipped at K == 1). Every lookup
+ * stays inside its event's segment, heads also break at an event boundary, and the three
+ * offset arrays are the existing exclusive sums read at row_off[e]. node_ptr holds global entry
+ * indices and one closing entry.
+ *   buf: the arrays at their bounds: row_off[K] rows (+ 1 for node_ptr), K + 1 per offset array.
+ * *out arrives with struct_size, abi_version and scored set, as for gtf_truth_concat, and leaves
+ * with the sums and buf's pointers. counts: a HOST array [K]; counts[e].error holds event e's
+ * GTF_TRUTH_ERR_* bits (one device word per event, touched only on a violation). A number of
+ * launches that does not depend on K, one synchronisation, nothing allocated. Nothing is
+ * written past node_id[sum T], node_ptr[sum T + 1], node_part[sum P], part_*[sum R] or an offset
+ * array's K + 1.
+ *   Returns -2 with the smallest failing event named: "event 3: a mapped hit has no truth row",
+ * "event 3: a volume_id, layer_id or module_id outside [0, 2^21)" (the arrays are then
+ * unspecified). -3 for another ABI of *in or *out; -2 for a null argument or array that is
+ * needed, a negative n_events, an offset array that does not start at 0 or decreases, a sum
+ * above 2^30 rows, min_volume > max_volume or a small workspace: all before any launch.
+ * K == 0 and events without rows, particles or truth rows are legal anywhere; with no rows at
+ * all the call writes the three zero offset arrays and node_ptr[0] = 0 and returns without a
+ * synchronisation (no column and no workspace needed). */
+int gtf_truth_build_ev(const gtf_truth_in_ev* in, const gtf_truth_batch_buf* buf, gtf_truth_batch* out,
+                       gtf_truth_counts* counts, void* workspace, size_t workspace_bytes,
+                       gtf_stream_t stream);
+
 /* ---- Parabolic-model KL training data -------------------------
  * learn_KL_parabolic_model/src/generate_training_data: the per-edge parabolic
  * state of compute_track_state_estimates (utils.py:221-289; S = diag(16, 0.01,
