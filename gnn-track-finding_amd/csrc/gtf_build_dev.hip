@@ -57,12 +57,7 @@ constexpr int32_t ERR_DUP = 1, ERR_RANGE = 2, ERR_ASYM = 4, ERR_OVER = 8;
 
 // first position in [b, e) of slot_src holding >= x
 __device__ inline int32_t lower(const int32_t* s, int32_t b, int32_t e, int32_t x) {
-    while (b < e) {
-        const int32_t m = (b + e) >> 1;
-        if (s[m] < x) b = m + 1;
-        else e = m;
-    }
-    return b;
+    return b + gtf::bound<false>(s + b, e - b, x);
 }
 
 __global__ void k_iota(int32_t* a, int64_t n) {
@@ -284,23 +279,11 @@ __global__ void k_tse_rank(const int32_t* order, int64_t n, const int32_t* slot_
 
 // ---- the batch forms: `off` [K + 1] are the events' offsets on the node or the row axis ----
 
-// the event whose range [off[e], off[e + 1]) holds i < off[K] (events without rows share an
-// offset: the last of them that starts at or before i is the one that holds it)
-__device__ inline int32_t event_of(const int32_t* off, int32_t K, int32_t i) {
-    int32_t lo = 0, hi = K - 1;
-    while (lo < hi) {
-        const int32_t m = (lo + hi) >> 1;
-        if (off[m + 1] <= i) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
-
 // the ids come sorted by id with the CSV index each came from: the event of every entry, the
 // key of the stable sort that makes it (event, id) order
 __global__ void k_event_keys(const int32_t* idx, int64_t n, const int32_t* noff, int32_t K, uint64_t* key) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) key[i] = (uint64_t)event_of(noff, K, idx[i]);
+    if (i < n) key[i] = (uint64_t)gtf::segment_of(noff, K, idx[i]);
 }
 
 __global__ void k_gather_ids(const int64_t* node_id, const int32_t* idx, int64_t n, uint64_t* ids) {
@@ -315,7 +298,7 @@ __global__ void k_check_ids_ev(const uint64_t* ids, int64_t n, const int32_t* no
     if (i >= n) return;
     if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, ERR_RANGE);
     if (i > 0 && ids[i] == ids[i - 1]) {
-        const int32_t e = event_of(noff, K, (int32_t)i);
+        const int32_t e = gtf::segment_of(noff, K, (int32_t)i);
         if (i > noff[e]) {
             atomicOr(err, ERR_DUP);
             atomicMin(err + 3, e);
@@ -328,7 +311,7 @@ __global__ void k_rows_ev(const int64_t* ra, const int64_t* rb, int64_t R, const
                           const int32_t* noff, const int32_t* roff, int32_t K, uint64_t* key, int32_t* t) {
     const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (r >= R) return;
-    const int32_t e = event_of(roff, K, (int32_t)r), lo = noff[e], hi = noff[e + 1];
+    const int32_t e = gtf::segment_of(roff, K, (int32_t)r), lo = noff[e], hi = noff[e + 1];
     const int32_t ia = find_id_in(ids, idx, lo, hi, ra[r]), ib = find_id_in(ids, idx, lo, hi, rb[r]);
     const bool ok = ia >= 0 && ib >= 0;
     key[2 * r] = ok ? ((uint64_t)ia << 32) | (uint32_t)ib : NONE;
@@ -340,7 +323,7 @@ __global__ void k_rows_ev(const int64_t* ra, const int64_t* rb, int64_t R, const
 // true when component c (its members from memb[lo] on, `sz` of them) gets CSV order: at least
 // half of its own event's nodes
 __device__ inline bool csv_order_ev(const int32_t* noff, int32_t K, int32_t member, int32_t sz) {
-    const int32_t e = event_of(noff, K, member);
+    const int32_t e = gtf::segment_of(noff, K, member);
     return 2 * (int64_t)sz >= (int64_t)(noff[e + 1] - noff[e]);
 }
 
@@ -368,7 +351,7 @@ __global__ void k_comp_order_ev(const int32_t* memb, const int32_t* coff, const 
     if (c >= n_sub) return;
     const int32_t lo = coff[c], sz = size[c], root = memb[lo];
     if (csv_order_ev(noff, K, root, sz)) return;
-    const int32_t e = event_of(noff, K, root);
+    const int32_t e = gtf::segment_of(noff, K, root);
     const int64_t cap = set_capacity(sz);
     int64_t* t = tbl + toff[c];
     DevSet s;
@@ -422,7 +405,7 @@ __global__ void k_tse_rank_ev(const int32_t* order, int64_t n, const int32_t* no
     if (p >= n) return;
     const int32_t b = slot_ptr[p], e = slot_ptr[p + 1], u = order[p];
     if (b < 0 || e < b || e > cap_out) { atomicOr(err, ERR_ASYM); return; }
-    const int32_t ev = event_of(noff, K, u), lo = noff[ev], hi = noff[ev + 1];
+    const int32_t ev = gtf::segment_of(noff, K, u), lo = noff[ev], hi = noff[ev + 1];
     const int64_t cap = set_capacity(e - b);
     DevSet s;
     s.init(tbl + toff[p], tbl + toff[p] + cap, cap);
@@ -448,7 +431,7 @@ __global__ void k_tse_rank_ev(const int32_t* order, int64_t n, const int32_t* no
 // positions [noff[e], noff[e + 1]): the event column is a function of the position
 __global__ void k_event_column(const int32_t* noff, int32_t K, int64_t n, int32_t* event) {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p < n) event[p] = event_of(noff, K, (int32_t)p);
+    if (p < n) event[p] = gtf::segment_of(noff, K, (int32_t)p);
 }
 
 struct BuildWs {

@@ -31,6 +31,7 @@
 
 #include "../../include/gtf.h"
 #include "gtf_host.h"
+#include "gtf_search.h"
 
 namespace {
 
@@ -40,7 +41,6 @@ using gtf::grid;
 
 constexpr int BLOCK = gtf::BLOCK256;
 constexpr int MAXC = GTF_CONCAT_MAX_COLUMNS;
-constexpr int LDS_OFFS = 2048;        // offsets staged in LDS when K + 1 <= this (8 KiB)
 constexpr int COPY_BLOCKS = 4096;     // blocks of a column launch, over its columns (16 a CU)
 constexpr int STRUCT_BLOCKS = 1024;   // blocks per axis of the structure launch
 constexpr int64_t LIMIT = (int64_t)1 << 31;
@@ -93,26 +93,6 @@ __global__ __launch_bounds__(BLOCK) void k_offsets(const gtf_concat_part* parts,
     if (t < AXES) off[(size_t)t * (K + 1) + K] = carry[t] < LIMIT ? (int32_t)carry[t] : INT32_MAX;
 }
 
-// the part of row r: the largest p in [0, K) with off[p] <= r (empty parts share their successor's offset
-// and are passed over); K >= 1
-__device__ __forceinline__ int find_part(const int32_t* off, int K, int r) {
-    int lo = 0, hi = K - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= r) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// the K + 1 offsets of one axis for this block: in LDS when they fit, else where they lie
-__device__ __forceinline__ const int32_t* stage_offsets(const int32_t* off, int K, int32_t* lds) {
-    if (K + 1 > LDS_OFFS) return off;
-    for (int i = threadIdx.x; i <= K; i += BLOCK) lds[i] = off[i];
-    __syncthreads();
-    return lds;
-}
-
 // ---- structure arrays ----
 struct Struct {
     int32_t K, N, S, E;   // the host's sums: no write beyond them
@@ -122,13 +102,13 @@ struct Struct {
 };
 
 __global__ __launch_bounds__(BLOCK) void k_struct(Struct a) {
-    __shared__ int32_t lds[LDS_OFFS];
+    __shared__ int32_t lds[gtf::LDS_OFFS];
     const int axis = blockIdx.y, K1 = a.K + 1;
     const int32_t* noff = a.off + (size_t)AX_NODE * K1;
     const int32_t* soff = a.off + (size_t)AX_SLOT * K1;
     const int32_t* eoff = a.off + (size_t)AX_EDGE * K1;
     const int32_t* boff = a.off + (size_t)AX_SUB * K1;
-    const int32_t* off = stage_offsets(a.off + (size_t)axis * K1, a.K, lds);
+    const int32_t* off = gtf::stage_offsets<BLOCK>(a.off + (size_t)axis * K1, a.K, lds);
     const int64_t rows = axis == AX_NODE ? (int64_t)a.N + 1 : axis == AX_SLOT ? a.S : a.E;
     for (int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x; r < rows; r += (int64_t)gridDim.x * BLOCK) {
         if (axis == AX_NODE && r == a.N) {   // the closing pointers
@@ -136,7 +116,7 @@ __global__ __launch_bounds__(BLOCK) void k_struct(Struct a) {
             if (a.o.out_ptr) a.o.out_ptr[a.N] = a.E;
             continue;
         }
-        const int p = find_part(off, a.K, (int)r);
+        const int p = gtf::segment_of(off, a.K, (int)r);
         const int l = (int)r - off[p];
         const gtf_concat_part q = a.parts[p];
         if (l < 0 || l >= part_size(q, axis)) continue;   // (the device table disagrees with the host's sums)
@@ -179,7 +159,7 @@ __device__ __forceinline__ void copy_tiles(const Col& c, const int32_t* off, int
         const int n = rows - r0 < BLOCK ? (int)(rows - r0) : BLOCK;
         if ((int)threadIdx.x < n) {
             const int r = (int)r0 + threadIdx.x;
-            const int p = find_part(off, K, r);
+            const int p = gtf::segment_of(off, K, r);
             const int l = r - off[p];
             s_part[threadIdx.x] = l >= 0 && l < off[p + 1] - off[p] ? p : -1;
             s_row[threadIdx.x] = l;
@@ -212,12 +192,12 @@ __device__ __forceinline__ void copy_words(const Col& c, const int32_t* off, int
 }
 
 __global__ __launch_bounds__(BLOCK) void k_columns(const int32_t* offs, int K, int N, int S, ColTab tab) {
-    __shared__ int32_t lds[LDS_OFFS];
+    __shared__ int32_t lds[gtf::LDS_OFFS];
     __shared__ int32_t s_part[BLOCK], s_row[BLOCK];
     const Col c = tab.c[blockIdx.y];
     const int axis = c.mode & 0xff, lg = c.mode >> 8;
     const int64_t rows = axis == 0 ? N : S;
-    const int32_t* off = stage_offsets(offs + (size_t)(axis == 0 ? AX_NODE : AX_SLOT) * (K + 1), K, lds);
+    const int32_t* off = gtf::stage_offsets<BLOCK>(offs + (size_t)(axis == 0 ? AX_NODE : AX_SLOT) * (K + 1), K, lds);
     if (lg == 3) copy_words<uint64_t>(c, off, K, rows, s_part, s_row);
     else if (lg == 2) copy_words<uint32_t>(c, off, K, rows, s_part, s_row);
     else copy_words<uint8_t>(c, off, K, rows, s_part, s_row);
@@ -280,12 +260,7 @@ __global__ __launch_bounds__(BLOCK) void k_split_check(Split a) {
         else {
             const int32_t ev = a.event[v];
             wrong |= ev < 0 || ev >= a.K;
-            int lo = 0, hi = l.n_groups - 1;   // the member's group: the last one that starts at or before it
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (l.ptr[mid] <= i) lo = mid;
-                else hi = mid - 1;
-            }
+            const int lo = gtf::segment_of(l.ptr, l.n_groups, i);   // the member's group
             wrong |= l.n_groups <= 0 || group_event(a, l, lo) != ev;          // one event per group
         }
     }

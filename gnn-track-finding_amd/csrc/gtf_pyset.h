@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gtf_search.h"
+
 namespace {
 
 // final table size of a CPython 3.10 set after n distinct insertions (start 8, resize when
@@ -95,27 +97,16 @@ struct DevSet {
     }
 };
 
-// index of node id `key` (ids sorted ascending, idx the index each came from), -1 if absent
-__device__ inline int32_t find_id(const uint64_t* ids, const int32_t* idx, int32_t n, int64_t key) {
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t m = (lo + hi) >> 1;
-        if (ids[m] < (uint64_t)key) lo = m + 1;
-        else hi = m;
-    }
-    return (lo < n && ids[lo] == (uint64_t)key) ? idx[lo] : -1;
-}
-
 // find_id inside the segment [lo, hi) of a map sorted by (event, id): the index of `key`
 // among one event's nodes, -1 if that event does not hold it (another one may)
 __device__ inline int32_t find_id_in(const uint64_t* ids, const int32_t* idx, int32_t lo, int32_t hi, int64_t key) {
-    const int32_t end = hi;
-    while (lo < hi) {
-        const int32_t m = (lo + hi) >> 1;
-        if (ids[m] < (uint64_t)key) lo = m + 1;
-        else hi = m;
-    }
-    return (lo < end && ids[lo] == (uint64_t)key) ? idx[lo] : -1;
+    const int32_t at = lo + gtf::bound<false>(ids + lo, hi - lo, (uint64_t)key);
+    return (at < hi && ids[at] == (uint64_t)key) ? idx[at] : -1;
+}
+
+// index of node id `key` (ids sorted ascending, idx the index each came from), -1 if absent
+__device__ inline int32_t find_id(const uint64_t* ids, const int32_t* idx, int32_t n, int64_t key) {
+    return find_id_in(ids, idx, 0, n, key);
 }
 
 }  // namespace

@@ -82,7 +82,11 @@ def test_the_table_of_batches_is_complete():
     names = set(BC.BATCHES)
     for n in BC.PLAIN:
         assert {"alone_" + n, "twice_" + n, "thrice_" + n} <= names
-    assert len(BC.PLAIN) == 17 and len(BC.RAISING) == 4
+    assert {"singleton_" + n for n in TC.CASES} <= names
+    singles = [n for n in BC.RAISING if n.startswith("singleton_")]
+    assert sorted(singles) == ["singleton_range_module", "singleton_range_volume", "singleton_truth_missing"]
+    assert all(BC.BATCHES[n]()["raises"][0] == 0 for n in singles)
+    assert len(BC.PLAIN) == 17 and len(BC.RAISING) == 4 + len(singles)
     for n in ("empty_first", "empty_middle", "empty_last", "only_empty", "none_between", "truth_beside_own",
               "no_particles_beside", "pt_differs", "hit_in_neighbours_only", "node_with_other_hits",
               "reference_here_repeat_there", "range_module_in_event_2", "range_volume_in_event_2", "runs_beside_one_row",
@@ -144,7 +148,7 @@ def _segment_bounds(sorted_keys, off, ev, keys):
 
 
 def batch_rule(batch):
-    """gtf_truth_ev.hip's steps on global indices -> the nine arrays, n_reference per event"""
+    """gtf_truth.hip's steps on global indices -> the nine arrays, n_reference per event"""
     lo, hi = batch["window"]
     live = [c for c in batch["events"]]
     K = len(live)

@@ -1,7 +1,8 @@
 """Batches of events for the batched truth tables (gtf.metrics.truth_tables_batch on the host,
 gtf_truth_build_ev / gtf.metrics.truth_tables_batch_dev on the device), made from tests/truth_cases.py.
 A batch has one volume window, so the cases are grouped by theirs: the (7, 7) cases, the (7, 8) ones
-(`reference` and the random events), and each `window_*` variant alone.
+(`reference` and the random events), and each `window_*` variant alone; every case is also a batch
+of its own (`singleton_*`), so the batch entry point runs each single-event case.
 
 A batch: "events" (truth_cases cases, or None for an event without truth), "window", and where the
 device path must refuse it "raises": (the event the error names, "missing" | "range").
@@ -26,6 +27,13 @@ def parts(batch):
 def _raising(name):
     e = TC.CASES[name]()["expect"]
     return bool(e.get("raises") or e.get("dev_raises"))
+
+
+def _singleton_raises(name):
+    """what a batch of this case alone raises: the host's ValueError is the missing truth row, the
+    device-only refusal the packed key's range"""
+    e = TC.CASES[name]()["expect"]
+    return (0, "missing") if e.get("raises") else (0, "range") if e.get("dev_raises") else None
 
 
 PLAIN = sorted(n for n in TC.CASES if not _raising(n))
@@ -114,6 +122,8 @@ def _random(seed):
 
 def _make():
     b = {}
+    for n in TC.CASES:       # every case of truth_cases.py as a batch of one event; a raising case names event 0
+        b["singleton_" + n] = lambda n=n: _batch(_named(n), raises=_singleton_raises(n))
     for n in PLAIN:
         b["alone_" + n] = lambda n=n: _batch(_named(n))
         b["twice_" + n] = lambda n=n: _batch(_named(n, n))
