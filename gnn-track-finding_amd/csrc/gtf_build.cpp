@@ -110,9 +110,7 @@ class PySet {
 extern "C" {
 
 int gtf_build_event_csr(gtf_event_csr* ev) {
-    if (!ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
-        (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
-        (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot))) {
+    if (gtf::bad_event_csr(ev)) {
         gtf::set_error("gtf_build_event_csr: bad arguments");
         return -2;
     }

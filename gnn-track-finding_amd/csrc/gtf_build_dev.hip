@@ -31,10 +31,13 @@
 // A batch of events (gtf_build_events_csr_device) is the same build on the events' columns
 // laid end to end: a graph whose components never cross an event boundary. Its sorts, scans,
 // hook rounds, slot keys and out-lists run on global indices as they are and leave the arrays
-// gtf/graph.py concat defines; three steps know the event of what they handle and have a
-// batch form beside the single-event kernel (the *_ev kernels below): the id -> CSV index
-// map, sorted by (event, id) and searched inside the event's segment; the 2|c| >= |G| rule,
-// with |G| the node count of the component's own event; and the event column.
+// gtf/graph.py concat defines. There is one build: every kernel exists once, and the steps
+// that know the event of what they handle -- the id -> CSV index map, sorted by (event, id)
+// and searched inside the event's segment; the 2|c| >= |G| rule, with |G| the node count of
+// the component's own event -- ask an Events value for it. One event is the Events without
+// offset tables: event 0, the nodes [0, N), nothing read. What only a batch has is on the
+// host side of build_csr: the offset upload, the second sort of the id map by event (from
+// two events on), the event column and the event in the duplicate-id message.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -53,7 +56,7 @@ constexpr int BLOCK = gtf::BLOCK256;
 constexpr uint64_t NONE = ~uint64_t(0);
 constexpr int32_t ERR_DUP = 1, ERR_RANGE = 2, ERR_ASYM = 4, ERR_OVER = 8;
 
-// set_capacity, DevSet (CPython 3.10 set) and find_id (node id -> CSV index): gtf_pyset.h
+// set_capacity, DevSet (CPython 3.10 set) and find_id_in (node id -> CSV index): gtf_pyset.h
 
 // first position in [b, e) of slot_src holding >= x
 __device__ inline int32_t lower(const int32_t* s, int32_t b, int32_t e, int32_t x) {
@@ -65,20 +68,51 @@ __global__ void k_iota(int32_t* a, int64_t n) {
     if (i < n) a[i] = (int32_t)i;
 }
 
-__global__ void k_check_ids(const uint64_t* ids, int64_t n, int32_t* err) {
+// The events a kernel works on, by value. One event: K == 0 and no tables -- event 0, the nodes
+// [0, n), nothing read (a branch every thread of a launch takes the same way). A batch: the K
+// events' offsets on the node and the row axis, [K + 1] each, in the workspace.
+struct Events {
+    const int32_t* noff;
+    const int32_t* roff;
+    int32_t K;
+    int32_t n;   // nodes of all events
+
+    __device__ int32_t of_node(int32_t i) const { return K ? gtf::segment_of(noff, K, i) : 0; }
+    __device__ int32_t of_row(int32_t r) const { return K ? gtf::segment_of(roff, K, r) : 0; }
+    // the nodes [lo, hi) of event e: its segment of the id map, and its |G|
+    __device__ void nodes(int32_t e, int32_t& lo, int32_t& hi) const {
+        lo = K ? noff[e] : 0;
+        hi = K ? noff[e + 1] : n;
+    }
+};
+
+// ids in (event, id) order: event e's are positions [lo, hi) of ev.nodes(e). A repeated id is
+// an error inside one event only; err[3] keeps the first such event.
+__global__ void k_check_ids(const uint64_t* ids, int64_t n, Events ev, int32_t* err) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, ERR_RANGE);   // also catches negatives
-    if (i > 0 && ids[i] == ids[i - 1]) atomicOr(err, ERR_DUP);
+    if (i > 0 && ids[i] == ids[i - 1]) {
+        const int32_t e = ev.of_node((int32_t)i);
+        int32_t lo, hi;
+        ev.nodes(e, lo, hi);
+        if (i > lo) {
+            atomicOr(err, ERR_DUP);
+            atomicMin(err + 3, e);
+        }
+    }
 }
 
-// both directions of row r at times 2r (a -> b) and 2r + 1 (b -> a); rows naming a node
-// outside the window are dropped (helper.py:512-518 adds edges between kept nodes only)
+// both directions of row r at times 2r (a -> b) and 2r + 1 (b -> a), both ends looked up among
+// the nodes of the row's own event; rows naming a node outside the window are dropped
+// (helper.py:512-518 adds edges between kept nodes only)
 __global__ void k_rows(const int64_t* ra, const int64_t* rb, int64_t R, const uint64_t* ids, const int32_t* idx,
-                       int32_t n, uint64_t* key, int32_t* t) {
+                       Events ev, uint64_t* key, int32_t* t) {
     const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (r >= R) return;
-    const int32_t ia = find_id(ids, idx, n, ra[r]), ib = find_id(ids, idx, n, rb[r]);
+    int32_t lo, hi;
+    ev.nodes(ev.of_row((int32_t)r), lo, hi);
+    const int32_t ia = find_id_in(ids, idx, lo, hi, ra[r]), ib = find_id_in(ids, idx, lo, hi, rb[r]);
     const bool ok = ia >= 0 && ib >= 0;
     key[2 * r] = ok ? ((uint64_t)ia << 32) | (uint32_t)ib : NONE;
     key[2 * r + 1] = ok ? ((uint64_t)ib << 32) | (uint32_t)ia : NONE;
@@ -148,37 +182,50 @@ __global__ void k_comp_of(const int32_t* lab, const int32_t* rank, int64_t n, in
     atomicAdd(&size[c], 1);
 }
 
-// members of every component in CSV-index order (the stable sort by component): the
-// copy's node order when 2|c| >= |G|
-__global__ void k_order_sorted(const int32_t* memb, const int32_t* comp, const int32_t* size, int64_t n,
-                               int32_t* order) {
+// members of every component in CSV-index order (the stable sort by component): the copy's
+// node order when 2|c| >= |G|. Written everywhere (k_comp_order then overwrites the components
+// under half of their event), so `order` is a permutation whatever comes after.
+__global__ void k_order_sorted(const int32_t* memb, int64_t n, int32_t* order) {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t g = memb[p];
-    if (2 * (int64_t)size[comp[g]] >= n) order[p] = g;
+    if (p < n) order[p] = memb[p];
 }
 
-__global__ void k_comp_words(const int32_t* size, int32_t n_sub, int64_t n, int64_t* words) {
+// true when the component of `sz` nodes holding `member` keeps CSV order: at least half of its
+// own event's nodes. `e`: that event.
+__device__ inline bool csv_order(const Events& ev, int32_t member, int32_t sz, int32_t& e) {
+    int32_t lo, hi;
+    e = ev.of_node(member);
+    ev.nodes(e, lo, hi);
+    return 2 * (int64_t)sz >= (int64_t)(hi - lo);
+}
+
+__global__ void k_comp_words(const int32_t* size, const int32_t* coff, const int32_t* memb, int32_t n_sub, Events ev,
+                             int64_t* words) {
     const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
     if (c > n_sub) return;
-    words[c] = (c < n_sub && 2 * (int64_t)size[c] < n) ? 3 * set_capacity(size[c]) : 0;
+    int32_t e;
+    words[c] = (c < n_sub && !csv_order(ev, memb[coff[c]], size[c], e)) ? 3 * set_capacity(size[c]) : 0;
 }
 
-// one thread per component smaller than half the graph: BFS from its root in successor
+// one thread per component smaller than half of its event: BFS from its root in successor
 // order into set(...) (nx.weakly_connected_components: set(_plain_bfs(G, root))), then the
-// copy's node order = the order of a second set filled from the first (show_nodes)
-__global__ void k_comp_order(const int32_t* memb, const int32_t* coff, const int32_t* size, int32_t n_sub, int64_t n,
-                             const int32_t* gptr, const uint64_t* gkey, const int32_t* gdst, const int64_t* node_id,
-                             const uint64_t* ids, const int32_t* idx, const int64_t* toff, int64_t* tbl,
-                             int32_t* queue, uint8_t* seen, int32_t* order, int32_t* err) {
+// copy's node order = the order of a second set filled from the first (show_nodes); the
+// set's ids go back to CSV indices inside the event's segment of the map. The queue and the
+// written order stay inside the component's `sz` entries whatever the arrays hold.
+__global__ void k_comp_order(const int32_t* memb, const int32_t* coff, const int32_t* size, int32_t n_sub, Events ev,
+                             const int32_t* gptr, const int32_t* gdst, const int64_t* node_id, const uint64_t* ids,
+                             const int32_t* idx, const int64_t* toff, int64_t* tbl, int32_t* queue, uint8_t* seen,
+                             int32_t* order, int32_t* err) {
     const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
-    if (c >= n_sub || 2 * (int64_t)size[c] >= n) return;
-    const int32_t lo = coff[c], sz = size[c];
+    if (c >= n_sub) return;
+    const int32_t lo = coff[c], sz = size[c], root = memb[lo];
+    int32_t e, elo, ehi;
+    if (csv_order(ev, root, sz, e)) return;
+    ev.nodes(e, elo, ehi);
     const int64_t cap = set_capacity(sz);
     int64_t* t = tbl + toff[c];
     DevSet s;
     s.init(t, t + cap, cap);
-    const int32_t root = memb[lo];
     int32_t head = lo, tail = lo;
     seen[root] = 1;
     s.add(node_id[root]);
@@ -187,14 +234,13 @@ __global__ void k_comp_order(const int32_t* memb, const int32_t* coff, const int
         const int32_t v = queue[head++];
         for (int32_t j = gptr[v]; j < gptr[v + 1]; j++) {
             const int32_t w = gdst[j];
-            if (!seen[w]) {
+            if (!seen[w] && tail < lo + sz) {
                 seen[w] = 1;
                 s.add(node_id[w]);
                 queue[tail++] = w;
             }
         }
     }
-    (void)gkey;
     DevSet shown;
     int64_t* spare = (s.a == t) ? t + cap : t;   // the first set's spare table
     shown.init(spare, t + 2 * cap, cap);
@@ -202,8 +248,11 @@ __global__ void k_comp_order(const int32_t* memb, const int32_t* coff, const int
         if (s.a[i] >= 0) shown.add(s.a[i]);
     if (s.over || shown.over) { atomicOr(err, ERR_OVER); return; }
     int32_t r = lo;
-    for (int64_t i = 0; i <= shown.mask; i++)
-        if (shown.a[i] >= 0) order[r++] = find_id(ids, idx, (int32_t)n, shown.a[i]);
+    for (int64_t i = 0; i <= shown.mask; i++) {
+        if (shown.a[i] < 0) continue;
+        const int32_t g = find_id_in(ids, idx, elo, ehi, shown.a[i]);
+        if (g >= 0 && r < lo + sz) order[r++] = g;
+    }
 }
 
 __global__ void k_pos(const int32_t* order, const int32_t* comp, int64_t n, int32_t* pos, int32_t* sub_id) {
@@ -234,14 +283,16 @@ __global__ void k_outdeg(const int32_t* order, const int32_t* gdeg, int64_t n, i
     if (p <= n) od[p] = p < n ? gdeg[order[p]] : 0;
 }
 
-// out-list of packed sender p in G's successor order: the slot of p in each receiver
+// out-list of packed sender p in G's successor order: the slot of p in each receiver; the
+// write stays inside the `cap` entries of out_slot
 __global__ void k_out_slot(const uint64_t* gkey, const int32_t* gdst, const int32_t* gptr, int32_t m,
                            const int32_t* pos, const int32_t* slot_ptr, const int32_t* slot_src,
-                           const int32_t* out_ptr, int32_t* out_slot) {
+                           const int32_t* out_ptr, int32_t* out_slot, int64_t cap) {
     const int32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= m) return;
     const int32_t u = (int32_t)(gkey[i] >> 33), p = pos[u], q = pos[gdst[i]];
-    out_slot[out_ptr[p] + (i - gptr[u])] = lower(slot_src, slot_ptr[q], slot_ptr[q + 1], p);
+    const int64_t at = (int64_t)out_ptr[p] + (i - gptr[u]);
+    if (at >= 0 && at < cap) out_slot[at] = lower(slot_src, slot_ptr[q], slot_ptr[q + 1], p);
 }
 
 __global__ void k_tse_words(const int32_t* slot_ptr, int64_t n, int64_t* words) {
@@ -250,162 +301,19 @@ __global__ void k_tse_words(const int32_t* slot_ptr, int64_t n, int64_t* words) 
 }
 
 // track_state_estimates key order of packed node p: reversed(set(chain(pred, succ)))
-// with the copy's predecessors (slot order) then G's successors
-__global__ void k_tse_rank(const int32_t* order, int64_t n, const int32_t* slot_ptr, const int32_t* slot_src,
-                           const int32_t* gptr, const int32_t* gdst, const int32_t* pos, const int64_t* node_id,
-                           const uint64_t* ids, const int32_t* idx, const int64_t* toff, int64_t* tbl,
-                           int32_t* tse_rank, int32_t* err) {
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t b = slot_ptr[p], e = slot_ptr[p + 1], u = order[p];
-    const int64_t cap = set_capacity(e - b);
-    DevSet s;
-    s.init(tbl + toff[p], tbl + toff[p] + cap, cap);
-    for (int32_t k = b; k < e; k++) {
-        s.add(node_id[order[slot_src[k]]]);
-        tse_rank[k] = -1;
-    }
-    for (int32_t j = gptr[u]; j < gptr[u + 1]; j++) s.add(node_id[gdst[j]]);
-    if (s.over) { atomicOr(err, ERR_OVER); return; }
-    int32_t r = 0;
-    for (int64_t i = s.mask; i >= 0; i--) {   // reversed iteration order
-        if (s.a[i] < 0) continue;
-        const int32_t q = pos[find_id(ids, idx, (int32_t)n, s.a[i])];
-        const int32_t f = lower(slot_src, b, e, q);
-        if (f == e || slot_src[f] != q) { atomicOr(err, ERR_ASYM); return; }
-        tse_rank[f] = r++;
-    }
-}
-
-// ---- the batch forms: `off` [K + 1] are the events' offsets on the node or the row axis ----
-
-// the ids come sorted by id with the CSV index each came from: the event of every entry, the
-// key of the stable sort that makes it (event, id) order
-__global__ void k_event_keys(const int32_t* idx, int64_t n, const int32_t* noff, int32_t K, uint64_t* key) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) key[i] = (uint64_t)gtf::segment_of(noff, K, idx[i]);
-}
-
-__global__ void k_gather_ids(const int64_t* node_id, const int32_t* idx, int64_t n, uint64_t* ids) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) ids[i] = (uint64_t)node_id[idx[i]];
-}
-
-// ids in (event, id) order: event e's are positions [noff[e], noff[e + 1]). A repeated id is
-// an error inside one event only; err[3] keeps the first such event.
-__global__ void k_check_ids_ev(const uint64_t* ids, int64_t n, const int32_t* noff, int32_t K, int32_t* err) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (ids[i] >= ((uint64_t)1 << 61) - 1) atomicOr(err, ERR_RANGE);
-    if (i > 0 && ids[i] == ids[i - 1]) {
-        const int32_t e = gtf::segment_of(noff, K, (int32_t)i);
-        if (i > noff[e]) {
-            atomicOr(err, ERR_DUP);
-            atomicMin(err + 3, e);
-        }
-    }
-}
-
-// k_rows with both ends looked up among the nodes of the row's own event
-__global__ void k_rows_ev(const int64_t* ra, const int64_t* rb, int64_t R, const uint64_t* ids, const int32_t* idx,
-                          const int32_t* noff, const int32_t* roff, int32_t K, uint64_t* key, int32_t* t) {
-    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (r >= R) return;
-    const int32_t e = gtf::segment_of(roff, K, (int32_t)r), lo = noff[e], hi = noff[e + 1];
-    const int32_t ia = find_id_in(ids, idx, lo, hi, ra[r]), ib = find_id_in(ids, idx, lo, hi, rb[r]);
-    const bool ok = ia >= 0 && ib >= 0;
-    key[2 * r] = ok ? ((uint64_t)ia << 32) | (uint32_t)ib : NONE;
-    key[2 * r + 1] = ok ? ((uint64_t)ib << 32) | (uint32_t)ia : NONE;
-    t[2 * r] = (int32_t)(2 * r);
-    t[2 * r + 1] = (int32_t)(2 * r + 1);
-}
-
-// true when component c (its members from memb[lo] on, `sz` of them) gets CSV order: at least
-// half of its own event's nodes
-__device__ inline bool csv_order_ev(const int32_t* noff, int32_t K, int32_t member, int32_t sz) {
-    const int32_t e = gtf::segment_of(noff, K, member);
-    return 2 * (int64_t)sz >= (int64_t)(noff[e + 1] - noff[e]);
-}
-
-// CSV-index order everywhere (k_comp_order_ev then overwrites the components under half of
-// their event), so `order` is a permutation whatever comes after
-__global__ void k_order_sorted_ev(const int32_t* memb, int64_t n, int32_t* order) {
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p < n) order[p] = memb[p];
-}
-
-__global__ void k_comp_words_ev(const int32_t* size, const int32_t* coff, const int32_t* memb, int32_t n_sub,
-                                const int32_t* noff, int32_t K, int64_t* words) {
-    const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
-    if (c > n_sub) return;
-    words[c] = (c < n_sub && !csv_order_ev(noff, K, memb[coff[c]], size[c])) ? 3 * set_capacity(size[c]) : 0;
-}
-
-// k_comp_order for the components under half of their own event; the set's ids go back to
-// CSV indices inside that event's segment of the map
-__global__ void k_comp_order_ev(const int32_t* memb, const int32_t* coff, const int32_t* size, int32_t n_sub,
-                                const int32_t* noff, int32_t K, const int32_t* gptr, const int32_t* gdst,
-                                const int64_t* node_id, const uint64_t* ids, const int32_t* idx, const int64_t* toff,
-                                int64_t* tbl, int32_t* queue, uint8_t* seen, int32_t* order, int32_t* err) {
-    const int32_t c = blockIdx.x * BLOCK + threadIdx.x;
-    if (c >= n_sub) return;
-    const int32_t lo = coff[c], sz = size[c], root = memb[lo];
-    if (csv_order_ev(noff, K, root, sz)) return;
-    const int32_t e = gtf::segment_of(noff, K, root);
-    const int64_t cap = set_capacity(sz);
-    int64_t* t = tbl + toff[c];
-    DevSet s;
-    s.init(t, t + cap, cap);
-    int32_t head = lo, tail = lo;
-    seen[root] = 1;
-    s.add(node_id[root]);
-    queue[tail++] = root;
-    while (head < tail) {
-        const int32_t v = queue[head++];
-        for (int32_t j = gptr[v]; j < gptr[v + 1]; j++) {
-            const int32_t w = gdst[j];
-            if (!seen[w] && tail < lo + sz) {
-                seen[w] = 1;
-                s.add(node_id[w]);
-                queue[tail++] = w;
-            }
-        }
-    }
-    DevSet shown;
-    int64_t* spare = (s.a == t) ? t + cap : t;   // the first set's spare table
-    shown.init(spare, t + 2 * cap, cap);
-    for (int64_t i = 0; i <= s.mask; i++)
-        if (s.a[i] >= 0) shown.add(s.a[i]);
-    if (s.over || shown.over) { atomicOr(err, ERR_OVER); return; }
-    int32_t r = lo;
-    for (int64_t i = 0; i <= shown.mask; i++) {
-        if (shown.a[i] < 0) continue;
-        const int32_t g = find_id_in(ids, idx, noff[e], noff[e + 1], shown.a[i]);
-        if (g >= 0 && r < lo + sz) order[r++] = g;
-    }
-}
-
-// k_out_slot with the write clamped to the `cap` entries of out_slot
-__global__ void k_out_slot_ev(const uint64_t* gkey, const int32_t* gdst, const int32_t* gptr, int32_t m,
-                              const int32_t* pos, const int32_t* slot_ptr, const int32_t* slot_src,
-                              const int32_t* out_ptr, int32_t* out_slot, int64_t cap) {
-    const int32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= m) return;
-    const int32_t u = (int32_t)(gkey[i] >> 33), p = pos[u], q = pos[gdst[i]];
-    const int64_t at = (int64_t)out_ptr[p] + (i - gptr[u]);
-    if (at >= 0 && at < cap) out_slot[at] = lower(slot_src, slot_ptr[q], slot_ptr[q + 1], p);
-}
-
-// k_tse_rank with the keys looked up inside the node's own event
-__global__ void k_tse_rank_ev(const int32_t* order, int64_t n, const int32_t* noff, int32_t K, const int32_t* slot_ptr,
-                              const int32_t* slot_src, const int32_t* gptr, const int32_t* gdst, const int32_t* pos,
-                              const int64_t* node_id, const uint64_t* ids, const int32_t* idx, const int64_t* toff,
-                              int64_t* tbl, int32_t* tse_rank, int64_t cap_out, int32_t* err) {
+// with the copy's predecessors (slot order) then G's successors, the keys looked up inside the
+// node's own event. Slots outside the `cap_out` entries of tse_rank, or a key that is no node
+// of the event, are ERR_ASYM.
+__global__ void k_tse_rank(const int32_t* order, int64_t n, Events ev, const int32_t* slot_ptr,
+                           const int32_t* slot_src, const int32_t* gptr, const int32_t* gdst, const int32_t* pos,
+                           const int64_t* node_id, const uint64_t* ids, const int32_t* idx, const int64_t* toff,
+                           int64_t* tbl, int32_t* tse_rank, int64_t cap_out, int32_t* err) {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     const int32_t b = slot_ptr[p], e = slot_ptr[p + 1], u = order[p];
     if (b < 0 || e < b || e > cap_out) { atomicOr(err, ERR_ASYM); return; }
-    const int32_t ev = gtf::segment_of(noff, K, u), lo = noff[ev], hi = noff[ev + 1];
+    int32_t lo, hi;
+    ev.nodes(ev.of_node(u), lo, hi);
     const int64_t cap = set_capacity(e - b);
     DevSet s;
     s.init(tbl + toff[p], tbl + toff[p] + cap, cap);
@@ -427,6 +335,20 @@ __global__ void k_tse_rank_ev(const int32_t* order, int64_t n, const int32_t* no
     }
 }
 
+// ---- a batch of two events or more: the id map from id order to (event, id) order ----
+
+// the ids come sorted by id with the CSV index each came from: the event of every entry, the
+// key of the stable sort that makes it (event, id) order
+__global__ void k_event_keys(const int32_t* idx, int64_t n, const int32_t* noff, int32_t K, uint64_t* key) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) key[i] = (uint64_t)gtf::segment_of(noff, K, idx[i]);
+}
+
+__global__ void k_gather_ids(const int64_t* node_id, const int32_t* idx, int64_t n, uint64_t* ids) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) ids[i] = (uint64_t)node_id[idx[i]];
+}
+
 // components are ranked by their minimum global CSV index, so event e's packed nodes are the
 // positions [noff[e], noff[e + 1]): the event column is a function of the position
 __global__ void k_event_column(const int32_t* noff, int32_t K, int64_t n, int32_t* event) {
@@ -440,7 +362,7 @@ struct BuildWs {
     int32_t *gdeg, *gptr, *lab, *isroot, *rank, *comp, *size, *coff, *memb, *pos, *queue, *rdeg, *od;
     uint8_t* seen;
     int64_t *words, *toff, *tbl;
-    int32_t* scal;   // [0] error bits, [1] changed, [2] valid edges, [3] a batch's first event with a repeated id
+    int32_t* scal;   // [0] error bits, [1] changed, [2] valid edges, [3] the first event with a repeated id
     int32_t *noff, *roff;   // a batch: the events' node and row offsets, [K + 1] each
     gtf::Scratch cub;
     size_t tbl_words, total;
@@ -507,20 +429,14 @@ int say(int rc, const char* who, const char* what) {
     return rc;
 }
 
-bool bad_event_args(const gtf_event_csr* ev, const void* workspace) {
-    return !ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
-           (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
-           (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot)) || !workspace;
-}
-
-// The build behind both entry points, their arguments checked. K == 0: one event, the
-// single-event kernels. K > 0: a batch of K events whose offsets noff / roff (host arrays)
-// go into the workspace first; the steps that know the event launch their *_ev form, every
-// other launch, sort, scan and synchronisation is the single event's.
+// The build behind both entry points, their arguments checked. K == 0: one event, no offset
+// tables. K > 0: a batch of K events whose offsets noff / roff (host arrays) go into the
+// workspace first. Every launch, sort, scan and synchronisation after the id map is the same.
 int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* roff, int32_t* event, const char* who,
               const BuildWs& w, hipStream_t st) {
     const int64_t N = ev->n_nodes, R = ev->n_rows, E2 = 2 * R;
     const gtf::Cub cub{w.cub, st};
+    const Events evs{w.noff, w.roff, K, (int32_t)N};
     // a failure that is not a HIP call's: -1 with its own text
     auto broken = [who](const char* what) { return say(-1, who, what); };
     hipError_t e;
@@ -538,36 +454,31 @@ int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* 
     const int64_t M2 = N > E2 ? N : E2;
     // 1. ids -> CSV index
     hipLaunchKernelGGL(k_iota, dim3(grid(M2)), dim3(BLOCK), 0, st, w.iota, M2);
-    if (K == 0) {
-        if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.ids, w.iota, w.idx, (int)N)) != hipSuccess)
-            return fail(who, "sort ids", e);
-        hipLaunchKernelGGL(k_check_ids, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.scal);
-    } else {
-        // ids of different events collide and cannot be shifted apart (both set orders hash the id
-        // itself): the id sort, then a stable sort by the event over the bits K needs, leaves event
-        // e's ids ascending at [noff[e], noff[e + 1])
-        if ((e = hipMemcpyAsync(w.noff, noff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess ||
-            (e = hipMemcpyAsync(w.roff, roff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess)
-            return fail(who, "offsets", e);
+    if (K > 0 &&
+        ((e = hipMemcpyAsync(w.noff, noff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess ||
+         (e = hipMemcpyAsync(w.roff, roff, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess))
+        return fail(who, "offsets", e);
+    // ids of different events collide and cannot be shifted apart (both set orders hash the id
+    // itself): from two events on the id sort, then a stable sort by the event over the bits K
+    // needs, leaves event e's ids ascending at [noff[e], noff[e + 1])
+    const bool by_event = K > 1;
+    if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, by_event ? w.kb : w.ids, w.iota, by_event ? w.va : w.idx,
+                            (int)N)) != hipSuccess)
+        return fail(who, "sort ids", e);
+    if (by_event) {
         int bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < K) bits++;
-        if ((e = cub.sort_pairs((const uint64_t*)ev->node_id, w.kb, w.iota, w.va, (int)N)) != hipSuccess)
-            return fail(who, "sort ids", e);
         hipLaunchKernelGGL(k_event_keys, dim3(grid(N)), dim3(BLOCK), 0, st, w.va, N, w.noff, K, w.ka);
         if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.idx, (int)N, bits)) != hipSuccess) return fail(who, "sort events", e);
         hipLaunchKernelGGL(k_gather_ids, dim3(grid(N)), dim3(BLOCK), 0, st, ev->node_id, w.idx, N, w.ids);
-        hipLaunchKernelGGL(k_check_ids_ev, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, w.noff, K, w.scal);
-        if (event) hipLaunchKernelGGL(k_event_column, dim3(grid(N)), dim3(BLOCK), 0, st, w.noff, K, N, event);
     }
+    hipLaunchKernelGGL(k_check_ids, dim3(grid(N)), dim3(BLOCK), 0, st, w.ids, N, evs, w.scal);
+    if (K > 0 && event) hipLaunchKernelGGL(k_event_column, dim3(grid(N)), dim3(BLOCK), 0, st, w.noff, K, N, event);
     // 2. G's successor lists in insertion order
     int32_t m = 0;
     if (R > 0) {
-        if (K == 0)
-            hipLaunchKernelGGL(k_rows, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx,
-                               (int32_t)N, w.ka, w.va);
-        else
-            hipLaunchKernelGGL(k_rows_ev, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx,
-                               w.noff, w.roff, K, w.ka, w.va);
+        hipLaunchKernelGGL(k_rows, dim3(grid(R)), dim3(BLOCK), 0, st, ev->row_a, ev->row_b, R, w.ids, w.idx, evs, w.ka,
+                           w.va);
         if ((e = cub.sort_pairs(w.ka, w.kb, w.va, w.vb, (int)E2)) != hipSuccess) return fail(who, "sort pairs", e);
         hipLaunchKernelGGL(k_first, dim3(grid(E2)), dim3(BLOCK), 0, st, w.kb, w.vb, E2, w.ka, w.va);
         if ((e = cub.sort_pairs(w.ka, w.gk, w.va, w.gv, (int)E2)) != hipSuccess) return fail(who, "sort succ", e);
@@ -612,16 +523,12 @@ int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* 
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
     if ((e = cub.scan(w.size, w.coff, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     // 4. node order of every component's copy: CSV-index order (the stable sort by
-    // component), replaced by the set order for components under half the graph
+    // component), replaced by the set order for components under half of their event (|G| of
+    // the 2|c| >= |G| rule: the node count of the component's own event)
     if ((e = cub.sort_pairs(w.ka, w.kb, w.iota, w.memb, (int)N, 32)) != hipSuccess) return fail(who, "sort members", e);
-    if (K == 0) {
-        hipLaunchKernelGGL(k_order_sorted, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, w.comp, w.size, N, ev->order);
-        hipLaunchKernelGGL(k_comp_words, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, n_sub, N, w.words);
-    } else {   // |G| of the 2|c| >= |G| rule: the node count of the component's own event
-        hipLaunchKernelGGL(k_order_sorted_ev, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, N, ev->order);
-        hipLaunchKernelGGL(k_comp_words_ev, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, w.coff, w.memb, n_sub,
-                           w.noff, K, w.words);
-    }
+    hipLaunchKernelGGL(k_order_sorted, dim3(grid(N)), dim3(BLOCK), 0, st, w.memb, N, ev->order);
+    hipLaunchKernelGGL(k_comp_words, dim3(grid(n_sub + 1)), dim3(BLOCK), 0, st, w.size, w.coff, w.memb, n_sub, evs,
+                       w.words);
     if ((e = cub.scan(w.words, w.toff, n_sub + 1)) != hipSuccess) return fail(who, "scan", e);
     int64_t words = 0;
     if ((e = hipMemcpyAsync(&words, w.toff + n_sub, 8, hipMemcpyDeviceToHost, st)) != hipSuccess)
@@ -629,13 +536,8 @@ int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* 
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
     if ((size_t)words > w.tbl_words) return broken("set tables exceed the workspace bound");
     if ((e = hipMemsetAsync(w.seen, 0, N, st)) != hipSuccess) return fail(who, "memset", e);
-    if (K == 0)
-        hipLaunchKernelGGL(k_comp_order, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub, N, w.gptr,
-                           gkey, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen, ev->order, w.scal);
-    else
-        hipLaunchKernelGGL(k_comp_order_ev, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub,
-                           w.noff, K, w.gptr, gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen,
-                           ev->order, w.scal);
+    hipLaunchKernelGGL(k_comp_order, dim3(grid(n_sub)), dim3(BLOCK), 0, st, w.memb, w.coff, w.size, n_sub, evs, w.gptr,
+                       gdst, ev->node_id, w.ids, w.idx, w.toff, w.tbl, w.queue, w.seen, ev->order, w.scal);
     hipLaunchKernelGGL(k_pos, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, w.comp, N, w.pos, ev->sub_id);
     // 5. slots: (packed receiver, packed sender) in order; the out-lists; the key orders
     if ((e = hipMemsetAsync(w.rdeg, 0, 4 * (N + 1), st)) != hipSuccess) return fail(who, "memset", e);
@@ -647,24 +549,16 @@ int build_csr(gtf_event_csr* ev, int32_t K, const int32_t* noff, const int32_t* 
     if ((e = cub.scan(w.rdeg, ev->slot_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     hipLaunchKernelGGL(k_outdeg, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->order, w.gdeg, N, w.od);
     if ((e = cub.scan(w.od, ev->out_ptr, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
-    if (m > 0 && K == 0)
+    if (m > 0)
         hipLaunchKernelGGL(k_out_slot, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, w.gptr, m, w.pos, ev->slot_ptr,
-                           ev->slot_src, ev->out_ptr, ev->out_slot);
-    else if (m > 0)
-        hipLaunchKernelGGL(k_out_slot_ev, dim3(grid(m)), dim3(BLOCK), 0, st, gkey, gdst, w.gptr, m, w.pos,
-                           ev->slot_ptr, ev->slot_src, ev->out_ptr, ev->out_slot, E2);
+                           ev->slot_src, ev->out_ptr, ev->out_slot, E2);
     hipLaunchKernelGGL(k_tse_words, dim3(grid(N + 1)), dim3(BLOCK), 0, st, ev->slot_ptr, N, w.words);
     if ((e = cub.scan(w.words, w.toff, (int)N + 1)) != hipSuccess) return fail(who, "scan", e);
     if ((e = hipMemcpyAsync(&words, w.toff + N, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
     if ((size_t)words > w.tbl_words) return broken("set tables exceed the workspace bound");
-    if (K == 0)
-        hipLaunchKernelGGL(k_tse_rank, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, ev->slot_ptr, ev->slot_src,
-                           w.gptr, gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank, w.scal);
-    else
-        hipLaunchKernelGGL(k_tse_rank_ev, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, w.noff, K, ev->slot_ptr,
-                           ev->slot_src, w.gptr, gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank,
-                           E2, w.scal);
+    hipLaunchKernelGGL(k_tse_rank, dim3(grid(N)), dim3(BLOCK), 0, st, ev->order, N, evs, ev->slot_ptr, ev->slot_src,
+                       w.gptr, gdst, w.pos, ev->node_id, w.ids, w.idx, w.toff, w.tbl, ev->tse_rank, E2, w.scal);
     if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
     if ((e = hipMemcpyAsync(scal, w.scal, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "read", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "sync", e);
@@ -685,7 +579,7 @@ size_t gtf_build_event_device_workspace_bytes(int64_t n_nodes, int64_t n_rows) {
 
 int gtf_build_event_csr_device(gtf_event_csr* ev, void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
     const char* who = "gtf_build_event_csr_device";
-    if (bad_event_args(ev, workspace)) return say(-2, who, "bad arguments");
+    if (gtf::bad_event_csr(ev) || !workspace) return say(-2, who, "bad arguments");
     const int64_t N = ev->n_nodes, R = ev->n_rows;
     if (N > INT32_MAX / 2 || 2 * R > INT32_MAX / 2) return say(-2, who, "graph too large for int32 indices");
     if (workspace_bytes < carve_bytes(N, R))
@@ -701,7 +595,7 @@ int gtf_build_events_csr_device(gtf_event_csr* ev, const gtf_event_batch* b, voi
                                 gtf_stream_t stream) {
     const char* who = "gtf_build_events_csr_device";
     if (const int rc = gtf::check_abi(b, who, "gtf_event_batch", "batch")) return rc;
-    if (bad_event_args(ev, workspace) || b->n_events < 0 || !b->node_off || !b->row_off)
+    if (gtf::bad_event_csr(ev) || !workspace || b->n_events < 0 || !b->node_off || !b->row_off)
         return say(-2, who, "bad arguments");
     const int64_t N = ev->n_nodes, R = ev->n_rows;
     const int32_t K = b->n_events;

@@ -49,6 +49,14 @@ int check_abi(const T* s, const char* who, const char* type, const char* null_wh
 // every entry point taking a gtf_graph
 inline int check_abi(const gtf_graph* g, const char* who) { return check_abi(g, who, "gtf_graph", "graph"); }
 
+// a gtf_event_csr neither event builder (gtf_build.cpp, gtf_build_dev.hip) can work on: null,
+// a negative size, or without a column or an output that its sizes call for
+inline bool bad_event_csr(const gtf_event_csr* ev) {
+    return !ev || ev->n_nodes < 0 || ev->n_rows < 0 || (ev->n_nodes && !ev->node_id) ||
+           (ev->n_rows && (!ev->row_a || !ev->row_b)) || !ev->order || !ev->sub_id || !ev->slot_ptr || !ev->out_ptr ||
+           (ev->n_rows && (!ev->slot_src || !ev->tse_rank || !ev->out_slot));
+}
+
 // ---- launches of 256 threads, one per item ----
 constexpr int BLOCK256 = 256;
 inline int grid(int64_t n) { return (int)((n + BLOCK256 - 1) / BLOCK256); }

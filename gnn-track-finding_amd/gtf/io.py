@@ -273,6 +273,32 @@ def build_networkx(event_prefix: str, min_volume: int, max_volume: int, truth_cs
     return [G.subgraph(c).copy() for c in nx.weakly_connected_components(G)]
 
 
+BATCH_CSR = ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank", "out_ptr", "out_slot")   # gtf_event_csr's outputs
+
+
+def _csr_capacity(N, R):
+    """the entries a builder wants behind every output of BATCH_CSR (never none)"""
+    return dict(zip(BATCH_CSR, (max(N, 1), max(N, 1), N + 1, max(2 * R, 1), max(2 * R, 1), N + 1, max(2 * R, 1))))
+
+
+def _device_event(ids, a, b, ws_bytes, device):
+    """What both device builds hand their entry point: the columns on ``device``, zeroed outputs at
+    _csr_capacity, a workspace of ``ws_bytes`` and the GtfEventCsr over them. Returns (ev, outputs,
+    (workspace, its bytes, stream) -- the call's last arguments, tensors to keep until it returns)."""
+    import ctypes
+    import torch
+    from . import _native as nat
+    N, R = int(ids.size), int(a.size)
+    cols = [torch.from_numpy(x).to(device) for x in (ids, a, b)]
+    o = {k: torch.zeros(n, dtype=torch.int32, device=device) for k, n in _csr_capacity(N, R).items()}
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    ev = nat.GtfEventCsr(N, R, vp(cols[0]) if N else None, vp(cols[1]) if R else None, vp(cols[2]) if R else None,
+                         *[vp(o[k]) for k in BATCH_CSR], 0, 0, 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    return ev, o, (vp(ws), ws_bytes, stream), cols + [ws]
+
+
 def csr_from_rows(ids, a, b, device=None):
     """The packed CSR of an event from its columns (node ids in CSV order; edge rows
     add_edge(a, b) then add_edge(b, a)): gtf_build_event_csr on the host, or
@@ -283,31 +309,17 @@ def csr_from_rows(ids, a, b, device=None):
     N, R = int(ids.size), int(a.size)
     ids = np.ascontiguousarray(ids, np.int64)
     a, b = np.ascontiguousarray(a, np.int64), np.ascontiguousarray(b, np.int64)
-    shapes = {"order": max(N, 1), "sub_id": max(N, 1), "slot_ptr": N + 1, "out_ptr": N + 1,
-              "slot_src": max(2 * R, 1), "tse_rank": max(2 * R, 1), "out_slot": max(2 * R, 1)}
-    names = ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank", "out_ptr", "out_slot")
+    L = nat.lib()
     if device is None:
-        o = {k: np.zeros(n, np.int32) for k, n in shapes.items()}
+        o = {k: np.zeros(n, np.int32) for k, n in _csr_capacity(N, R).items()}
         vp = lambda t: ctypes.c_void_p(t.ctypes.data)  # noqa: E731
         ev = nat.GtfEventCsr(N, R, vp(ids) if N else None, vp(a) if R else None, vp(b) if R else None,
-                             *[vp(o[k]) for k in names], 0, 0, 0)
-        nat.check(nat.lib().gtf_build_event_csr(ctypes.byref(ev)))
+                             *[vp(o[k]) for k in BATCH_CSR], 0, 0, 0)
+        nat.check(L.gtf_build_event_csr(ctypes.byref(ev)))
         return o, int(ev.n_edges), int(ev.n_subgraphs)
-    import torch
-    L = nat.lib()
-    t_ids, t_a, t_b = (torch.from_numpy(x).to(device) for x in (ids, a, b))
-    o = {k: torch.zeros(n, dtype=torch.int32, device=device) for k, n in shapes.items()}
-    ws_bytes = int(L.gtf_build_event_device_workspace_bytes(N, R))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    ev = nat.GtfEventCsr(N, R, vp(t_ids) if N else None, vp(t_a) if R else None, vp(t_b) if R else None,
-                         *[vp(o[k]) for k in names], 0, 0, 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    nat.check(L.gtf_build_event_csr_device(ctypes.byref(ev), vp(ws), ws_bytes, stream))
+    ev, o, tail, _keep = _device_event(ids, a, b, int(L.gtf_build_event_device_workspace_bytes(N, R)), device)
+    nat.check(L.gtf_build_event_csr_device(ctypes.byref(ev), *tail))
     return {k: v.cpu().numpy() for k, v in o.items()}, int(ev.n_edges), int(ev.n_subgraphs)
-
-
-BATCH_CSR = ("order", "sub_id", "slot_ptr", "slot_src", "tse_rank", "out_ptr", "out_slot")
 
 
 def csr_from_rows_batch(parts, device=None):
@@ -358,20 +370,13 @@ def csr_from_rows_batch(parts, device=None):
         raise ValueError("csr_from_rows_batch: the batch is too large for int32 indices")
     L = nat.lib()
     cat = lambda i: np.concatenate([p[i] for p in parts]) if parts else np.zeros(0, np.int64)  # noqa: E731
-    t_ids, t_a, t_b = (torch.from_numpy(cat(i)).to(device) for i in range(3))
-    shapes = {"order": max(N, 1), "sub_id": max(N, 1), "slot_ptr": N + 1, "out_ptr": N + 1,
-              "slot_src": max(2 * R, 1), "tse_rank": max(2 * R, 1), "out_slot": max(2 * R, 1)}
-    o = {k: torch.zeros(n, dtype=torch.int32, device=device) for k, n in shapes.items()}
+    ev, o, tail, _keep = _device_event(cat(0), cat(1), cat(2), int(L.gtf_build_events_device_workspace_bytes(N, R, K)),
+                                       device)
     event = torch.zeros(max(N, 1), dtype=torch.int32, device=device)
-    ws_bytes = int(L.gtf_build_events_device_workspace_bytes(N, R, K))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     no, ro = node_off.astype(np.int32), row_off.astype(np.int32)
-    ev = nat.GtfEventCsr(N, R, vp(t_ids) if N else None, vp(t_a) if R else None, vp(t_b) if R else None,
-                         *[vp(o[k]) for k in BATCH_CSR], 0, 0, 0)
-    bt = nat.GtfEventBatch(n_events=K, node_off=no.ctypes.data, row_off=ro.ctypes.data, event=vp(event))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    nat.check(L.gtf_build_events_csr_device(ctypes.byref(ev), ctypes.byref(bt), vp(ws), ws_bytes, stream))
+    bt = nat.GtfEventBatch(n_events=K, node_off=no.ctypes.data, row_off=ro.ctypes.data,
+                           event=ctypes.c_void_p(event.data_ptr()))
+    nat.check(L.gtf_build_events_csr_device(ctypes.byref(ev), ctypes.byref(bt), *tail))
     E, n_sub = int(ev.n_edges), int(ev.n_subgraphs)
     size = {"order": N, "sub_id": N, "slot_ptr": N + 1, "out_ptr": N + 1, "slot_src": E, "tse_rank": E, "out_slot": E}
     out = {k: o[k][:size[k]].cpu().numpy() for k in BATCH_CSR}

@@ -30,7 +30,7 @@ gtf_score_finish returns the matched particles in match order; no candidate list
 to the host. :func:`truth_tables_dev` builds those tables on the device as well
 (gtf_truth_build, csrc/gtf_truth.hip), from the columns uploaded once: the same arrays.
 For a batch of events :func:`truth_tables_batch_dev` builds the tables of all of them in one call
-(gtf_truth_build_ev, csrc/gtf_truth_ev.hip): what truth_concat_dev of the per-event tables leaves.
+(gtf_truth_build_ev, csrc/gtf_truth.hip): what truth_concat_dev of the per-event tables leaves.
 """
 from __future__ import annotations
 
@@ -628,7 +628,7 @@ class DeviceTruthBatch:
 
 
 def truth_concat_dev(tables, device="cuda", mem: str = "torch") -> DeviceTruthBatch:
-    """concat_tables on the device (gtf_truth_concat, csrc/gtf_score_ev.hip): two launches whatever the
+    """concat_tables on the device (gtf_truth_concat, csrc/gtf_score.hip): two launches whatever the
     number of events, nothing synchronises. Entries may be TruthTables (uploaded), DeviceTruth
     (truth_tables_dev: used where it is) or None (an event without truth). One allocator and one device:
     that of the DeviceTruth entries, which must agree, else ``device`` / ``mem``."""
@@ -720,7 +720,7 @@ def _gather_dev(mm: _Mem, cols, dtypes, axes, n0, n1):
 
 
 def truth_tables_batch_dev(parts, min_volume: int, max_volume: int, device="cuda", mem: str = "torch") -> DeviceTruthBatch:
-    """truth_tables_batch on the device in ONE build (gtf_truth_build_ev, csrc/gtf_truth_ev.hip): what
+    """truth_tables_batch on the device in ONE build (gtf_truth_build_ev, csrc/gtf_truth.hip): what
     truth_concat_dev([truth_tables_dev(...) for each part]) leaves, word for word, with one synchronisation
     and a number of launches that does not depend on len(parts). The columns are all host arrays
     (concatenated, and uploaded once per column: eleven uploads whatever K) or all device arrays of this
@@ -838,7 +838,7 @@ def truth_files_batch_dev(prefixes, mapping: str, min_volume: int, max_volume: i
 
 
 class BatchScorer:
-    """DeviceScorer for the K events of a fused graph at once (gtf_score_*_ev, csrc/gtf_score_ev.hip): one
+    """DeviceScorer for the K events of a fused graph at once (gtf_score_*_ev, csrc/gtf_score.hip): one
     add() per iteration takes the fused graph's candidates as gtf_extract_outputs and gtf_event_split
     left them -- the global cand_ptr / cand_ids and cand_first (extract.split_dev: "cand_first_dev") --
     and results() returns one Result per event, equal to what DeviceScorer.result() gives for that event

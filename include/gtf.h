@@ -820,7 +820,7 @@ int gtf_score_finish(const gtf_truth* truth, const gtf_score_state* state, uint6
  * compute, in launch sequences whose length does not depend on K. Node ids and particle ids of
  * different events collide (the same event twice is the plain case), so the K truth tables are
  * not merged: they lie end to end and every lookup stays inside its own event's segment, as
- * gtf_candidate_order_device_ev looks node ids up. gtf_score_ev.hip.
+ * gtf_candidate_order_device_ev looks node ids up. gtf_score.hip.
  *
  * gtf_truth_batch: the K gtf_truth tables end to end, DEVICE arrays. node_id and part_id
  * ascend inside an event's segment only; node_ptr holds every event's pointers shifted by its
@@ -1047,7 +1047,7 @@ int gtf_truth_build(const gtf_truth_in* in, const gtf_truth_buf* buf, gtf_truth*
  * gtf/metrics.py truth_tables_batch (reconstruction_efficiency.py:41-91, helper.py:466-479 per
  * event) on the device: the parsed columns of K events laid end to end go in, and what comes
  * out is the gtf_truth_batch that gtf_truth_concat of the K single gtf_truth_build results
- * leaves, word for word. gtf_truth_ev.hip.
+ * leaves, word for word. gtf_truth.hip.
  *
  * One window and one cut per batch. Event e's mapping rows are row_off[e] .. row_off[e + 1]
  * of the six mapping columns, its truth rows truth_off[e] .. truth_off[e + 1] of truth_hit /

@@ -13,48 +13,17 @@ import pytest
 import batch_cases as bc
 import build_batch_cases as bb
 import real800 as R
+from guard_mem import Mem as _Mem, at, untouched as _untouched
 from gtf import _native as nat
 from gtf import io
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256   # (a multiple of the arena's alignment: the workspace between its guards stays aligned)
 KEYS = io.BATCH_CSR
 BATCH = [("vol7",), ("hand", "perm257"), ("empty",), ("vol7",)]   # the list tests/test_gpu_batch.py runs
 
 
 # ---------------------------------------------------------------- 1. the C-ABI between guard bytes
-class _Mem:
-    """device buffers of one allocator: "torch" tensors or "hip" (gtf.devmem) arrays"""
-
-    def __init__(self, mem):
-        self.mem = mem
-        if mem == "torch":
-            import torch
-            self.torch = torch
-            self.stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        else:
-            self.stream = ctypes.c_void_p(0)
-
-    def up(self, a):
-        a = np.ascontiguousarray(a).reshape(-1)
-        if self.mem == "torch":
-            return self.torch.from_numpy(a).cuda()
-        from gtf.devmem import HipArray
-        return HipArray.from_numpy(a)
-
-    def host(self, t):
-        return t.cpu().numpy() if self.mem == "torch" else t.numpy()
-
-    def guarded(self, nbytes):
-        return self.up(np.full(GUARD + nbytes + GUARD, 0xA5, np.uint8))
-
-    def payload(self, t, nbytes, dtype=np.int32):
-        h = self.host(t)
-        assert bool((h[:GUARD] == 0xA5).all()) and bool((h[GUARD + nbytes:] == 0xA5).all()), "guard bytes"
-        return h[GUARD:GUARD + nbytes].view(dtype)
-
-
 def _abi(parts, mem, tamper=None, ws_short=0):
     """gtf_build_events_csr_device on raw buffers: every output, the event column and the workspace lie
     between guard bytes. Returns (status, outputs as host arrays at their allocated sizes, n_edges, n_sub)."""
@@ -71,7 +40,6 @@ def _abi(parts, mem, tamper=None, ws_short=0):
     out = {k: m.guarded(4 * n) for k, n in size.items()}
     nb = int(L.gtf_build_events_device_workspace_bytes(N, Rr, K))
     ws = m.guarded(nb)
-    at = lambda t: ctypes.c_void_p(t.data_ptr() + GUARD)  # noqa: E731
     ev = nat.GtfEventCsr(N, Rr, ids.data_ptr(), a.data_ptr(), b.data_ptr(), *[at(out[k]) for k in KEYS], 0, 0, 0)
     bt = nat.GtfEventBatch(n_events=K, node_off=node_off.ctypes.data, row_off=row_off.ctypes.data, event=at(out["event"]))
     if tamper:
@@ -111,10 +79,6 @@ def test_duplicate_id_inside_an_event_names_it():
         io.csr_from_rows_batch(bb.DUP_INSIDE, device="cuda")
     rc, _, _, _ = _abi([bb.part([1, 2]), bb.part([3, -4])], "torch")
     assert rc == -2 and b"2^61" in nat.lib().gtf_last_error()
-
-
-def _untouched(got):
-    return all(bool((v.view(np.uint8) == 0xA5).all()) for v in got.values())
 
 
 def test_host_refusals_leave_the_outputs_untouched():
