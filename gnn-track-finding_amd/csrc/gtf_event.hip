@@ -18,6 +18,8 @@
 //         or y*y lies so close to a rounding midpoint that the C library's pow(x, 2), which
 //         defines r (io.edge_length_xy), may round the other way; gtf_event_radius_patch
 //         scatters the caller's r of those nodes. One synchronisation, for the two counts.
+//         A batch (gtf_event_window_ev) is the same two launches on the batch's rows and one
+//         gather of the sum at the events' K + 1 row offsets: the kept rows per event.
 //
 // Plain loads, vector stores, consecutive lanes on consecutive destination words; no atomics,
 // no allocation; pack and fill do not synchronise.
@@ -25,6 +27,8 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <vector>
 
 #include "../../include/gtf.h"
 #include "gtf_host.h"
@@ -121,16 +125,23 @@ __global__ __launch_bounds__(BLOCK) void k_fill(ColTab tab) {
 // ---- window ----
 struct WinWs {
     int64_t *in, *sum;   // [n + 1] kept | ambiguous << 32; the exclusive sum
+    int32_t* off;        // ev [K + 1] the caller's row offsets
+    int64_t* at;         // ev [K + 1] the sum at the offsets
     gtf::Scratch cub;
     size_t total;
 };
 
-WinWs win_carve(void* base, int64_t n) {
-    WinWs w;
+// K: the events of a batch; -1: one event, no offsets
+WinWs win_carve(void* base, int64_t n, int64_t K) {
+    WinWs w = {};
     gtf::Arena a(base);
     const size_t n1 = (size_t)(n > 0 ? n : 0) + 1;
     w.in = a.take<int64_t>(n1);
     w.sum = a.take<int64_t>(n1);
+    if (K >= 0) {
+        w.off = a.take<int32_t>((size_t)K + 1);
+        w.at = a.take<int64_t>((size_t)K + 1);
+    }
     w.cub = gtf::CubNeed().scan<int64_t>((int)n1).take(a);
     w.total = a.used();
     return w;
@@ -191,6 +202,14 @@ __global__ __launch_bounds__(BLOCK) void k_window_scatter(Win a) {
     }
 }
 
+// a batch: the sum at the events' offsets
+__global__ __launch_bounds__(BLOCK) void k_window_events(Win a, int K) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e > K) return;
+    const int32_t r = a.w.off[e];
+    a.w.at[e] = a.w.sum[r < 0 ? 0 : r > a.n ? a.n : r];
+}
+
 __global__ __launch_bounds__(BLOCK) void k_radius_patch(double* r, int32_t n_nodes, const int32_t* index, const double* value,
                                                         int32_t n) {
     const int k = blockIdx.x * BLOCK + threadIdx.x;
@@ -203,45 +222,98 @@ __global__ __launch_bounds__(BLOCK) void k_radius_patch(double* r, int32_t n_nod
 
 extern "C" {
 
-size_t gtf_event_window_workspace_bytes(int32_t n_rows) { return win_carve(nullptr, n_rows).total; }
+size_t gtf_event_window_workspace_bytes(int32_t n_rows) { return win_carve(nullptr, n_rows, -1).total; }
 
-int gtf_event_window(const gtf_window_in* in, const gtf_window_out* out, gtf_window_counts* counts, void* workspace,
-                     size_t workspace_bytes, gtf_stream_t stream) {
-    const char* who = "gtf_event_window";
+size_t gtf_event_window_ev_workspace_bytes(int32_t n_rows, int32_t n_events) {
+    return win_carve(nullptr, n_rows, n_events > 0 ? n_events : 0).total;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Both entry points: row_off null is one event (K is not read), else the K events of a batch with
+// their kept rows in n_kept.
+int window(const char* who, const gtf_window_in* in, const int32_t* row_off, int32_t K, const gtf_window_out* out,
+           int32_t* n_kept, gtf_window_counts* counts, void* workspace, size_t workspace_bytes, gtf_stream_t stream) {
+    char m[200];
+    auto no = [&](const char* what) {
+        snprintf(m, sizeof(m), "%s: %s", who, what);
+        return bad(m);
+    };
     if (int rc = gtf::check_abi(in, who, "gtf_window_in", "gtf_window_in")) return rc;
-    if (!out || !counts) return bad("gtf_event_window: null out or counts");
-    if (in->n_rows < 0) return bad("gtf_event_window: negative n_rows");
-    if (in->n_rows > INT32_MAX / 4) return bad("gtf_event_window: event too large for int32 indices");
-    counts->n_kept = counts->n_ambiguous = 0;
+    if (!out || !counts) return no("null out or counts");
+    if (in->n_rows < 0) return no("negative n_rows");
+    if (in->n_rows > INT32_MAX / 4) return no("event too large for int32 indices");
     const int32_t n = in->n_rows;
+    const bool ev = row_off != nullptr;
+    if (ev) {
+        if (K > 0 && !n_kept) return no("null n_kept with n_events > 0");
+        if (row_off[0] != 0 || row_off[K] != n) return no("row_off does not run from 0 to n_rows");
+        for (int e = 0; e < K; e++)
+            if (row_off[e + 1] < row_off[e]) return no("row_off decreases");
+        for (int e = 0; e < K; e++) n_kept[e] = 0;
+    }
+    counts->n_kept = counts->n_ambiguous = 0;
     if (n == 0) return 0;
-    if (!in->node_idx || !in->layer_id || !in->x || !in->y || !in->z)
-        return bad("gtf_event_window: missing input column (node_idx, layer_id, x, y, z)");
+    if (!in->node_idx || !in->layer_id || !in->x || !in->y || !in->z) return no("missing input column (node_idx, layer_id, x, y, z)");
     if (!out->node_idx || !out->layer_id || !out->x || !out->y || !out->z || !out->r || !out->amb_index || !out->amb_x ||
         !out->amb_y)
-        return bad("gtf_event_window: missing array of gtf_window_out");
-    if (!workspace || workspace_bytes < gtf_event_window_workspace_bytes(n))
-        return bad("gtf_event_window: workspace smaller than gtf_event_window_workspace_bytes");
+        return no("missing array of gtf_window_out");
+    if (!workspace || workspace_bytes < win_carve(nullptr, n, ev ? K : -1).total)
+        return no(ev ? "workspace smaller than gtf_event_window_ev_workspace_bytes"
+                     : "workspace smaller than gtf_event_window_workspace_bytes");
     Win a;
     a.n = n; a.lo = in->lo; a.hi = in->hi;
     a.ids = in->node_idx; a.layer_id = in->layer_id; a.x = in->x; a.y = in->y; a.z = in->z;
     a.o = *out;
-    a.w = win_carve(workspace, n);
+    a.w = win_carve(workspace, n, ev ? K : -1);
     hipStream_t st = (hipStream_t)stream;
     const gtf::Cub cub{a.w.cub, st};
     hipError_t e;
+    if (ev && (e = hipMemcpyAsync(a.w.off, row_off, 4 * ((size_t)K + 1), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(who, "offsets", e);
     hipLaunchKernelGGL(k_window_flags, dim3(gtf::grid((int64_t)n + 1)), dim3(BLOCK), 0, st, a);
     if ((e = cub.scan(a.w.in, a.w.sum, n + 1)) != hipSuccess) return fail(who, "scan", e);
     hipLaunchKernelGGL(k_window_scatter, dim3(gtf::grid(n)), dim3(BLOCK), 0, st, a);
+    if (ev) hipLaunchKernelGGL(k_window_events, dim3(gtf::grid((int64_t)K + 1)), dim3(BLOCK), 0, st, a, K);
     if ((e = hipGetLastError()) != hipSuccess) return fail(who, "launch", e);
     int64_t total = 0;
-    if ((e = hipMemcpyAsync(&total, a.w.sum + n, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return fail(who, "counts", e);
+    std::vector<int64_t> at(ev ? (size_t)K + 1 : 0);
+    if (ev) e = hipMemcpyAsync(at.data(), a.w.at, 8 * at.size(), hipMemcpyDeviceToHost, st);
+    else e = hipMemcpyAsync(&total, a.w.sum + n, 8, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return fail(who, "counts", e);
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(who, "synchronize", e);
+    if (ev) total = at[K];
     const int64_t kept = (int64_t)(uint32_t)total, amb = (int64_t)((uint64_t)total >> 32);
-    if (kept > n || amb > kept) return bad("gtf_event_window: inconsistent counts");
+    if (kept > n || amb > kept) return no("inconsistent counts");
+    for (int f = 0; ev && f < K; f++) {
+        const int64_t k = (int64_t)(uint32_t)at[f + 1] - (int64_t)(uint32_t)at[f];
+        if (k < 0 || k > row_off[f + 1] - row_off[f]) return no("inconsistent counts");
+        n_kept[f] = (int32_t)k;
+    }
     counts->n_kept = (int32_t)kept;
     counts->n_ambiguous = (int32_t)amb;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gtf_event_window(const gtf_window_in* in, const gtf_window_out* out, gtf_window_counts* counts, void* workspace,
+                     size_t workspace_bytes, gtf_stream_t stream) {
+    return window("gtf_event_window", in, nullptr, 1, out, nullptr, counts, workspace, workspace_bytes, stream);
+}
+
+int gtf_event_window_ev(const gtf_window_in* in, const int32_t* row_off, int32_t n_events, const gtf_window_out* out,
+                        int32_t* n_kept, gtf_window_counts* counts, void* workspace, size_t workspace_bytes,
+                        gtf_stream_t stream) {
+    const char* who = "gtf_event_window_ev";
+    if (n_events < 0) return bad("gtf_event_window_ev: negative n_events");
+    static const int32_t none[1] = {0};
+    if (n_events > 0 && !row_off) return bad("gtf_event_window_ev: null row_off with n_events > 0");
+    return window(who, in, row_off ? row_off : none, n_events, out, n_kept, counts, workspace, workspace_bytes, stream);
 }
 
 int gtf_event_radius_patch(double* r, int32_t n_nodes, const int32_t* index, const double* value, int32_t n,

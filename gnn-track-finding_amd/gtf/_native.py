@@ -370,6 +370,24 @@ class GtfCsvCounts(ctypes.Structure):
                 ("first_bad_error", U32), ("pad_", I32)]
 
 
+class GtfCsvFile(ctypes.Structure):
+    """gtf_csv_file: one file of gtf_csv_parse_ev's host table"""
+    _fields_ = [("start", I32), ("n_bytes", I32)]
+
+
+class GtfCsvInEv(ctypes.Structure):
+    """gtf_csv_in_ev; keyword construction only -- struct_size / abi_version are filled in"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("text", P), ("files", P), ("row_off", P),
+                ("n_files", I32), ("skip_lines", I32), ("n_fields", I32), ("max_rows", I32), ("n_columns", I32),
+                ("delimiter", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 3),
+                ("columns", GtfCsvColumn * CSV_MAX_COLUMNS)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfCsvInEv)
+        self.abi_version = ABI_VERSION
+
+
 class GtfWindowIn(ctypes.Structure):
     """gtf_window_in; keyword construction only -- struct_size / abi_version are filled in"""
     _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_rows", I32), ("pad_", I32), ("lo", ctypes.c_int64),
@@ -469,7 +487,9 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_graph_subset_workspace_bytes", "gtf_graph_subset_plan", "gtf_graph_subset_apply",
            "gtf_subset_gather", "gtf_refresh_send_mw", "gtf_event_pack", "gtf_fill_columns",
            "gtf_csv_chunk_bytes", "gtf_csv_parse_workspace_bytes", "gtf_csv_parse",
+           "gtf_csv_parse_ev_workspace_bytes", "gtf_csv_parse_ev",
            "gtf_event_window_workspace_bytes", "gtf_event_window", "gtf_event_radius_patch",
+           "gtf_event_window_ev_workspace_bytes", "gtf_event_window_ev",
            "gtf_updated_state_pair_counts", "gtf_updated_state_distances", "gtf_set_diagnostics",
            "gtf_device_init", "gtf_malloc", "gtf_free", "gtf_memcpy_htod", "gtf_memcpy_dtoh", "gtf_memcpy_dtod",
            "gtf_memset", "gtf_stream_synchronize",
@@ -623,6 +643,13 @@ def lib(lean: bool = False):
     L.gtf_csv_parse_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_csv_parse_workspace_bytes.argtypes = [I32]
     L.gtf_csv_parse.argtypes = [ctypes.POINTER(GtfCsvIn), ctypes.POINTER(GtfCsvCounts), P, ctypes.c_size_t, P]
+    L.gtf_csv_parse_ev_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_csv_parse_ev_workspace_bytes.argtypes = [ctypes.c_int64, I32]
+    L.gtf_csv_parse_ev.argtypes = [ctypes.POINTER(GtfCsvInEv), ctypes.POINTER(GtfCsvCounts), P, ctypes.c_size_t, P]
+    L.gtf_event_window_ev_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_event_window_ev_workspace_bytes.argtypes = [I32, I32]
+    L.gtf_event_window_ev.argtypes = [ctypes.POINTER(GtfWindowIn), P, I32, ctypes.POINTER(GtfWindowOut), P,
+                                      ctypes.POINTER(GtfWindowCounts), P, ctypes.c_size_t, P]
     L.gtf_event_window_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_event_window_workspace_bytes.argtypes = [I32]
     L.gtf_event_window.argtypes = [ctypes.POINTER(GtfWindowIn), ctypes.POINTER(GtfWindowOut),
@@ -669,7 +696,8 @@ def lib(lean: bool = False):
                "gtf_score_candidates", "gtf_score_finish", "gtf_truth_build", "gtf_csv_parse", "gtf_event_window",
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
                "gtf_event_split", "gtf_build_events_csr_device", "gtf_truth_concat", "gtf_score_reset_ev",
-               "gtf_score_candidates_ev", "gtf_score_finish_ev", "gtf_truth_build_ev"):
+               "gtf_score_candidates_ev", "gtf_score_finish_ev", "gtf_truth_build_ev", "gtf_csv_parse_ev",
+               "gtf_event_window_ev"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

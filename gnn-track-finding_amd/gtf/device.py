@@ -1209,6 +1209,32 @@ class DeviceGraph:
         d.n_events, d.event_nodes = K, nn
         return d
 
+    @classmethod
+    def from_fused(cls, cols, node_off, row_off, device: str = "cuda", mem: str = "torch"):
+        """from_events for columns that are fused already: ``cols`` holds from_event's eight columns
+        (ids, x, y, z, r, layer_id, row_a, row_b) of K events end to end as device arrays, ``node_off``
+        and ``row_off`` (host, [K + 1], from 0, not decreasing) say where each event's nodes and rows
+        lie -- what io.read_nodes_batch_dev and io.read_edges_batch_dev return. No gather, no copy.
+        The rows of an event that keeps no node stay in the row columns (from_events drops them): they
+        name no node of their event, so gtf_build_events_csr_device drops every one of them and the
+        graph is from_events' graph, bit for bit."""
+        cols = tuple(cols)
+        if len(cols) != 8 or not all(hasattr(a, "data_ptr") for a in cols):
+            raise ValueError("from_fused: from_event's eight columns as device arrays")
+        node_off, row_off = (np.ascontiguousarray(o, np.int64).reshape(-1) for o in (node_off, row_off))
+        if node_off.size != row_off.size or node_off.size < 1:
+            raise ValueError("from_fused: node_off and row_off hold one entry per event and one more")
+        for o, a, what in ((node_off, cols[0], "node"), (row_off, cols[6], "row")):
+            if o[0] != 0 or (np.diff(o) < 0).any() or int(o[-1]) != int(a.numel()):
+                raise ValueError("from_fused: %s_off does not run from 0 to the %s count without decreasing" % (what, what))
+        N, R = int(node_off[-1]), int(row_off[-1])
+        if max(N, 2 * R) > (2 ** 31 - 1) // 2:
+            raise ValueError("from_fused: the batch is too large for int32 indices")
+        d = cls._from_event(*cols, device, mem, lambda part: None, shell=cls._event_shell(device, mem),
+                            batch=(node_off.astype(np.int32), row_off.astype(np.int32)))
+        d.n_events, d.event_nodes = node_off.size - 1, [int(n) for n in np.diff(node_off)]
+        return d
+
     @staticmethod
     def _gather_columns(c, parts, nn, nr, N, R):
         """the eight device columns of every part end to end: gtf_graph_concat with no structure output

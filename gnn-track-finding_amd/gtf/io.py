@@ -125,6 +125,95 @@ def read_edges_dev(data_or_path, device="cuda", mem: str = "torch"):
     return c[0], c[1], c.n_rows
 
 
+NODE_COLUMNS = (("node_idx", "int64"), ("layer_id", "int64"), ("x", "float64"), ("y", "float64"), ("z", "float64"))
+
+
+class DeviceNodesBatch(DeviceNodes):
+    """read_nodes_batch_dev's result: DeviceNodes for the kept nodes of K events end to end, with
+    ``node_off`` (host int32 [K + 1]: event e's nodes are node_off[e] .. node_off[e + 1]), ``parse``
+    (the ParsedBatch's info) and ``files`` / ``reasons`` (per file "device" or "host", and why)."""
+
+
+def read_nodes_batch_dev(files, min_volume: int, max_volume: int, device="cuda", mem: str = "torch", mark=None,
+                         keep_unpatched: bool = False) -> DeviceNodesBatch:
+    """read_nodes_dev for the nodes.csv of K events at once: ONE parse (csvdev.parse_batch_dev,
+    gtf_csv_parse_ev), ONE window (gtf_event_window_ev) and, for the whole batch, one download of the
+    ambiguous list, one edge_length_xy, one upload and one gtf_event_radius_patch. The six columns
+    hold read_nodes_dev's arrays of the files end to end, bit for bit. A file outside the parser's
+    exact domain, or headers that place the columns differently, make the parse go file by file
+    (the offending file through read_nodes's pandas parser); the window and the patch stay one call.
+    mark: called with "upload", "parse", "window", "patch" as each part is done."""
+    import ctypes
+    from . import _native as nat
+    from . import csvdev
+    from .metrics import _Mem
+    if min_volume < 0:
+        raise ValueError("read_nodes_batch_dev: negative min_volume")
+    mark = mark or (lambda part: None)
+    mm = _Mem(device, mem)
+    files = list(files)
+    K = len(files)
+
+    def host_reader(f):
+        import pandas as pd
+        from io import BytesIO
+        a = pd.read_csv(f if isinstance(f, str) else BytesIO(bytes(f)))
+        return [a[name].to_numpy(np.dtype(t)) for name, t in NODE_COLUMNS]
+
+    c = csvdev.parse_batch_dev(files, NODE_COLUMNS, 1, mm=mm, mark=mark, host_reader=host_reader)
+    n = c.n_rows
+    m1 = max(n, 1)
+    out = [mm.empty(m1, dt) for dt in (np.int64, np.int64, np.float64, np.float64, np.float64, np.float64, np.int32,
+                                       np.float64, np.float64)]
+    win = nat.GtfWindowIn(n_rows=n, lo=min_volume * 1000, hi=(max_volume + 1) * 1000,
+                          **{k: mm.p(c[k]) for k in ("node_idx", "layer_id", "x", "y", "z")})
+    wout = nat.GtfWindowOut(*(mm.p(a) for a in out))
+    nb = int(mm.lib.gtf_event_window_ev_workspace_bytes(n, K))
+    ws = mm.empty(nb, np.uint8)
+    cnt = nat.GtfWindowCounts()
+    row_off = np.ascontiguousarray(c.row_off, np.int32)
+    kept_ev = np.zeros(max(K, 1), np.int32)
+    nat.check(mm.lib.gtf_event_window_ev(ctypes.byref(win), row_off.ctypes.data, K, ctypes.byref(wout),
+                                         kept_ev.ctypes.data, ctypes.byref(cnt), mm.p(ws), ctypes.c_size_t(nb), mm.stream))
+    mark("window")
+    kept, amb = int(cnt.n_kept), int(cnt.n_ambiguous)
+    ids, lay, x, y, z, r = (mm.first(a, kept) for a in out[:6])
+    raw = None
+    if keep_unpatched:
+        raw = mm.host(r, kept, np.float64).copy()
+    if amb:
+        ax, ay = mm.host(out[7], amb, np.float64), mm.host(out[8], amb, np.float64)
+        val = mm.from_host(edge_length_xy(ax, ay))
+        nat.check(mm.lib.gtf_event_radius_patch(mm.p(r), kept, mm.p(out[6]), mm.p(val), amb, mm.stream))
+    if mm.torch is None:    # (the parsed columns, the workspace and val are freed at once: not stream-ordered)
+        nat.check(mm.lib.gtf_stream_synchronize(None))
+    mark("patch")
+    d = DeviceNodesBatch(mm, (ids, x, y, z, r, lay), kept, n, amb, raw)
+    d.node_off = np.concatenate([[0], np.cumsum(kept_ev[:K], dtype=np.int64)]).astype(np.int32)
+    d.row_off, d.parse, d.files, d.reasons = row_off, c.info, c.files, c.reasons
+    return d
+
+
+def read_edges_batch_dev(files, device="cuda", mem: str = "torch", mark=None):
+    """read_edges_dev for the edges.csv of K events at once: one csvdev.parse_batch_dev ->
+    (node2, node1, row_off, ParsedBatch): fused device columns and the host offsets of the events'
+    rows. A file outside the domain goes through read_edges, and every file is then parsed alone."""
+    from . import csvdev
+
+    def host_reader(f):
+        if isinstance(f, str):
+            return read_edges(f)
+        from io import BytesIO
+        fh = BytesIO(bytes(f))
+        fh.readline()
+        fh.readline()
+        e = np.loadtxt(fh, delimiter=",", dtype=np.float64, ndmin=2)
+        return e[:, 0].astype(np.int64), e[:, 1].astype(np.int64)
+
+    c = csvdev.parse_batch_dev(files, ((0, "int64"), (1, "int64")), 2, device, mem, mark=mark, host_reader=host_reader)
+    return c[0], c[1], np.ascontiguousarray(c.row_off, np.int32), c
+
+
 def load_event(event_prefix: str, min_volume: int, max_volume: int, params=None) -> TrackGraph:
     """``event_prefix`` like ``.../event_1_filtered_graph_`` (nodes.csv / edges.csv appended)."""
     from .synth import _assemble

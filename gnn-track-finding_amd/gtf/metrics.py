@@ -729,12 +729,28 @@ def truth_tables_batch_dev(parts, min_volume: int, max_volume: int, device="cuda
     return _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, lambda what: None)
 
 
-def _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, mark):
+def _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, mark, fused=None):
     """truth_tables_batch_dev; mark("build") / mark("built") are called around the library call
-    (tools/batch_truth.py records device events there)"""
+    (tools/batch_truth.py records device events there). fused: (the eleven device columns of the batch
+    end to end -- the six mapping columns, truth hit and particle, particle id, px, py; None for one
+    without rows --, row_off, truth_off, particle_off: host, [K + 1]) as csvdev.parse_batch_dev left
+    them; ``parts`` then only says which events are scored (None: not) and nothing is gathered."""
     from . import _native as nat
     parts = list(parts)
     K = len(parts)
+    if fused is not None:
+        if min_volume > max_volume:
+            raise ValueError("min_volume > max_volume")
+        dev, offs = list(fused[0]), [np.ascontiguousarray(o, np.int64).reshape(-1) for o in fused[1:]]
+        if len(dev) != 11 or len(offs) != 3 or any(o.size != K + 1 or o[0] != 0 or (np.diff(o) < 0).any() for o in offs):
+            raise ValueError("fused: eleven columns and three offset arrays of K + 1 entries from 0, not decreasing")
+        if max(int(o[-1]) for o in offs) > 1 << 30:
+            raise ValueError("more than 2^30 rows")
+        row_off, truth_off, particle_off = (np.ascontiguousarray(o, np.int32) for o in offs)
+        N, NT, NP = int(row_off[-1]), int(truth_off[-1]), int(particle_off[-1])
+        mm = _Mem(device, mem)
+        dev = [a if total else None for a, total in zip(dev, [N] * 6 + [NT] * 2 + [NP] * 3)] if N else [None] * 11
+        return _truth_build_ev(mm, parts, dev, row_off, truth_off, particle_off, min_volume, max_volume, mark)
     is_dev = lambda a: hasattr(a, "data_ptr")  # noqa: E731
     size = lambda a: 0 if a is None else int(a.numel()) if is_dev(a) else int(a.size)  # noqa: E731
     events = []      # per event its eleven columns (truth_hit / truth_part None: the mapping's own), or None
@@ -787,6 +803,14 @@ def _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, mark):
     else:
         dev = [mm.from_host(np.concatenate([a for a in c if a is not None])) if total else None
                for c, total in zip(per_column, [N] * 6 + [NT] * 2 + [NP] * 3)]
+    return _truth_build_ev(mm, parts, dev, row_off, truth_off, particle_off, min_volume, max_volume, mark)
+
+
+def _truth_build_ev(mm, parts, dev, row_off, truth_off, particle_off, min_volume, max_volume, mark):
+    """the one gtf_truth_build_ev of _truth_tables_batch_dev, on the batch's eleven device columns"""
+    nat = mm.nat
+    K = len(parts)
+    N, NT, NP = int(row_off[-1]), int(truth_off[-1]), int(particle_off[-1])
     names = MAPPING_COLUMNS + ("truth_hit", "truth_part", "part_id", "px", "py")
     tin = nat.GtfTruthInEv(n_events=K, num_layers=NUM_DISTINCT_LAYERS, min_volume=int(min_volume),
                            max_volume=int(max_volume), pt_cut=PT_CUT, row_off=row_off.ctypes.data,
@@ -817,11 +841,19 @@ def _truth_tables_batch_dev(parts, min_volume, max_volume, device, mem, mark):
     return DeviceTruthBatch(mm, out, batch, scored, n_reference, [d_scored, ws, dev])
 
 
-def truth_files_batch_dev(prefixes, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch"):
+def truth_files_batch_dev(prefixes, mapping: str, min_volume: int, max_volume: int, device="cuda", mem: str = "torch",
+                          batch_parse: bool = False):
     """truth_tables_batch_dev from the files of K events: each event's files are parsed as truth_files_dev
     parses them (per file, on the device; a file outside the parser's exact domain is read with
     pd.read_csv and uploaded), then ONE build makes the tables. ``prefixes``: one per event, or None for an
-    event without truth. Returns (DeviceTruthBatch, [truth_files_dev's info per event, None without truth])."""
+    event without truth. Returns (DeviceTruthBatch, [truth_files_dev's info per event, None without truth]).
+    batch_parse: the files of one kind -- the particles, the mappings, and the truth.csv of the events that
+    have one -- are each parsed in ONE call (csvdev.parse_batch_dev) and their fused columns go to the
+    build as they are, without a gather. The same tables, word for word, and the same infos; the
+    DeviceTruthBatch's ``parse_info`` holds the three ParsedBatch infos."""
+    if batch_parse:
+        return _truth_files_batch_parse(list(prefixes), mapping, min_volume, max_volume, device, mem,
+                                        lambda what: None)
     mm = _Mem(device, mem)
     parts, infos = [], []
     for prefix in prefixes:
@@ -980,3 +1012,49 @@ def summary(r: Result) -> Dict[str, object]:
     return {"reconstructed": r.n_reconstructed, "reference": r.n_reference, "efficiency_pct": r.efficiency_str,
             "mean_track_purity": float(np.mean(r.track_purities)) if r.track_purities.size else None,
             "mean_particle_purity": float(np.mean(r.particle_purities)) if r.particle_purities.size else None}
+
+
+def _truth_files_batch_parse(prefixes, mapping, min_volume, max_volume, device, mem, mark):
+    """truth_files_batch_dev(batch_parse=True); mark as _truth_tables_batch_dev's, and "parsed" once the
+    three kinds have been parsed"""
+    import os
+    from .csvdev import parse_batch_dev
+    mm = _Mem(device, mem)
+    K = len(prefixes)
+    live = [e for e, q in enumerate(prefixes) if q is not None]
+    with_truth = [e for e in live if os.path.isfile(prefixes[e] + "truth.csv")]
+    infos = [None if q is None else {} for q in prefixes]
+    batch_info, cols, offs = {}, {}, {}
+
+    def read(key, events, suffix, columns):
+        def host_reader(path):
+            import pandas as pd
+            f = pd.read_csv(path, usecols=[name for name, _ in columns])
+            return [f[name].to_numpy(np.dtype(t)) for name, t in columns]
+
+        c = parse_batch_dev([prefixes[e] + suffix for e in events], columns, 1, mm=mm, host_reader=host_reader)
+        batch_info[key] = c.info
+        sizes = np.zeros(K, np.int64)
+        for k, e in enumerate(events):
+            infos[e][key] = c.files[k]
+            if c.reasons[k]:
+                infos[e][key + "_reason"] = c.reasons[k]
+            sizes[e] = int(c.row_off[k + 1]) - int(c.row_off[k])
+        cols[key] = [c[name] for name, _ in columns]
+        offs[key] = np.concatenate([[0], np.cumsum(sizes)])
+
+    read("particles", live, "particles.csv", (("particle_id", "int64"), ("px", "float64"), ("py", "float64")))
+    read("mapping", live, mapping, tuple((c, "int64") for c in MAPPING_COLUMNS))
+    if with_truth:
+        read("truth", with_truth, "truth.csv", (("hit_id", "int64"), ("particle_id", "int64")))
+    else:
+        cols["truth"], offs["truth"] = [None, None], np.zeros(K + 1, np.int64)
+    for e in with_truth:    # (for the library no truth rows means "the mapping's own columns")
+        if offs["truth"][e + 1] == offs["truth"][e] and offs["mapping"][e + 1] > offs["mapping"][e]:
+            raise ValueError("event %d: a mapped hit has no truth row (helper.__get_particle_id .item())" % e)
+    mark("parsed")
+    d = _truth_tables_batch_dev([None if q is None else () for q in prefixes], min_volume, max_volume, device, mem, mark,
+                                fused=(cols["mapping"] + cols["truth"] + cols["particles"], offs["mapping"],
+                                       offs["truth"], offs["particles"]))
+    d.parse_info = batch_info
+    return d, infos

@@ -181,15 +181,37 @@ def _event_states(d, p):
 
 
 def build_events_dev(prefixes, min_volume: int, max_volume: int, p: Params = None, device="cuda",
-                     mem: str = "torch", parse: str = "host"):
+                     mem: str = "torch", parse: str = "host", batch_parse: bool = False):
     """build_event_dev for a batch of events in ONE build: every event's files are read as
     build_event_dev reads them (the device parse and its per-file host fallback stay per file;
     ``parse_info`` is the list of the events' records), DeviceGraph.from_events makes the fused graph --
     what DeviceGraph.concat of the events' build_event_dev graphs holds, bit for bit -- and the states,
     priors, mixture weights, degrees and send weights are computed ONCE on it. run_batch(d) runs the
-    loop on it without a concat; d.n_events and d.event_nodes say how it divides."""
+    loop on it without a concat; d.n_events and d.event_nodes say how it divides.
+    batch_parse (with parse="device"): the CSV front end is per batch too -- all nodes.csv in one
+    gtf_csv_parse_ev, one gtf_event_window_ev and one radius patch (io.read_nodes_batch_dev), all
+    edges.csv in one more parse (io.read_edges_batch_dev) -- and the fused columns go to
+    DeviceGraph.from_fused without a gather. The same graph, bit for bit; ``parse_info`` is again one
+    record per event, with "batch": the ParsedBatch infos of the two kinds."""
     from .device import DeviceGraph
     p = p or Params()
+    if batch_parse:
+        if parse != "device":
+            raise ValueError("batch_parse needs parse='device'")
+        from . import io
+        prefixes = list(prefixes)
+        nd = io.read_nodes_batch_dev([q + "nodes.csv" for q in prefixes], min_volume, max_volume, device, mem)
+        n2, n1, row_off, ed = io.read_edges_batch_dev([q + "edges.csv" for q in prefixes], device, mem)
+        d = DeviceGraph.from_fused((nd.ids, nd.x, nd.y, nd.z, nd.r, nd.layer_id, n1, n2), nd.node_off, row_off, device, mem)
+        d.parse_info = []
+        for e in range(len(prefixes)):
+            info = {"nodes": nd.files[e], "edges": ed.files[e], "batch": {"nodes": nd.parse, "edges": ed.info}}
+            if nd.reasons[e]:
+                info["nodes_reason"] = nd.reasons[e]
+            if ed.reasons[e]:
+                info["edges_reason"] = ed.reasons[e]
+            d.parse_info.append(info)
+        return _event_states(d, p)
     read = [_event_columns(prefix, min_volume, max_volume, device, mem, parse) for prefix in prefixes]
     d = DeviceGraph.from_events([cols for cols, _ in read], device, mem)
     d.parse_info = [info for _, info in read]

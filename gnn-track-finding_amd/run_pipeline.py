@@ -45,6 +45,10 @@ under every ROOTDIR/<i>/, byte for byte.
 --batch-truth (with --batch-metrics) makes the truth tables of the whole batch in ONE build as well
 (gtf.metrics.truth_tables_batch_dev: gtf_truth_build_ev on the events' columns laid end to end; with
 --resident-parse the truth files are parsed on the GPU first, per file). The same metrics.json files.
+--batch-parse (with --batch-build and --resident-parse) parses the batch's CSV files per kind instead of
+per file: all nodes.csv in ONE gtf_csv_parse_ev, one window and one radius patch, all edges.csv in one more
+parse (pipeline.build_events_dev(batch_parse=True)); with --batch-truth the particles, mapping and truth
+files too (gtf.metrics.truth_files_batch_dev(batch_parse=True)). The same files under every ROOTDIR/<i>/.
 
 --start S > 1 resumes from ROOTDIR/iteration_{S-1}/remaining/graph.npz, as the run
 script's commented "iteration by iteration" mode does (:79-81).
@@ -140,7 +144,8 @@ def _tables_batch(args, truth):
     from gtf import metrics
     pres = [os.path.join(t, "event000001000-") if t else None for t in truth]
     if args.resident_parse:
-        batch, infos = metrics.truth_files_batch_dev(pres, args.mapping, args.min_volume, args.max_volume, args.device)
+        batch, infos = metrics.truth_files_batch_dev(pres, args.mapping, args.min_volume, args.max_volume, args.device,
+                                                     batch_parse=args.batch_parse)
         for i, info in enumerate(infos):
             for key in ("particles", "mapping", "truth"):
                 if info and key in info:
@@ -224,6 +229,10 @@ def main(argv=None):
                     help="with --batch-metrics: the truth tables of the whole batch come from one build "
                          "(gtf.metrics.truth_tables_batch_dev) instead of one per event and a concat; the same "
                          "metrics.json files")
+    ap.add_argument("--batch-parse", action="store_true",
+                    help="with --batch-build and --resident-parse: the CSV files of the batch are parsed per kind in "
+                         "one call each (gtf_csv_parse_ev) instead of per file; with --batch-truth the truth files "
+                         "too; the same files")
     ap.add_argument("--truth", nargs="+", metavar="DIR",
                     help="EVENT_TRUTH dir: score the candidates (reconstruction_efficiency.py); with --batch one "
                          "directory for every event, or one per event")
@@ -246,6 +255,8 @@ def main(argv=None):
         ap.error("--batch-metrics scores the events of --batch against --truth")
     if args.batch_truth and not args.batch_metrics:
         ap.error("--batch-truth builds the truth tables of --batch-metrics")
+    if args.batch_parse and not (args.batch_build and args.resident_parse):
+        ap.error("--batch-parse parses the files of --batch-build --resident-parse")
     if args.resident_parse:
         args.resident_event = True
     if args.resident_event and args.start != 1:
@@ -346,7 +357,8 @@ def _batch(args, p, ex):
         t0 = time.perf_counter()
         fused = pipeline.build_events_dev([os.path.join(dn, "event_1_filtered_graph_") for dn in args.batch],
                                           args.min_volume, args.max_volume, p, args.device,
-                                          parse="device" if args.resident_parse else "host")
+                                          parse="device" if args.resident_parse else "host",
+                                          batch_parse=args.batch_parse)
         if args.resident_parse:
             for info in fused.parse_info:
                 for key in ("nodes", "edges"):

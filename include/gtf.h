@@ -1466,6 +1466,68 @@ size_t gtf_csv_parse_workspace_bytes(int32_t n_bytes);
 int gtf_csv_parse(const gtf_csv_in* in, gtf_csv_counts* counts, void* workspace, size_t workspace_bytes,
                   gtf_stream_t stream);
 
+/* ---- a batch's files of one kind in one call: gtf_csv_parse_ev ---------------------------
+ * K files with the same field layout lie in ONE device text buffer, file e at files[e].start
+ * with files[e].n_bytes bytes. The requested columns come back with the files' rows laid end to
+ * end: file e's rows are row_off[e] .. row_off[e + 1] of every column, each exactly what
+ * gtf_csv_parse gives on that file alone. The same kernels as gtf_csv_parse (which is the batch
+ * of one without tables), one more small launch and one more scan, whatever K is.
+ *
+ * The table `files` is HOST memory. Every start is a multiple of gtf_csv_chunk_bytes() (so it is
+ * 16-byte aligned with the text) and the starts ascend: a file with bytes starts at or behind
+ * the end of the one before it, rounded up to a chunk, so every chunk belongs to one file. A
+ * file of 0 bytes takes no chunk and may stand anywhere; its start must still be a multiple of
+ * the chunk. The last file's end obeys the bound of gtf_csv_in.n_bytes.
+ *
+ * Bytes outside a file are never read as text: whatever precedes a file's first byte and whatever
+ * follows its last one, padding or the next file, reads as '\n'. The padding between files may
+ * hold anything.
+ *
+ * skip_lines holds for every file on its own: rows[e] = max(lines[e] - skip_lines, 0). A file
+ * with fewer lines contributes no row and does not shift its neighbours.
+ *
+ * counts is HOST memory, [n_files]: n_rows, the error bits and the first offending (row, field)
+ * of every file, the row counted inside the file after its skipped lines. An error in file e
+ * leaves every other file's rows exact; only e's rows are unspecified. max_rows is the size of
+ * the columns for the whole batch: the file whose row would be row max_rows of the batch gets
+ * GTF_CSV_ERR_ROWS at that row's index inside the file, every later file that has rows gets it
+ * at its row 0, and the files in front of it are exact. */
+typedef struct gtf_csv_file {
+    int32_t start;               /* first byte in the text: a multiple of gtf_csv_chunk_bytes() */
+    int32_t n_bytes;
+} gtf_csv_file;
+
+typedef struct gtf_csv_in_ev {
+    uint32_t struct_size;        /* sizeof(gtf_csv_in_ev) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    const char* text;            /* the buffer, device, 16-byte aligned */
+    const gtf_csv_file* files;   /* [n_files], HOST, starts ascending */
+    int32_t* row_off;            /* out, optional: [n_files + 1] device, the files' first rows */
+    int32_t n_files;
+    int32_t skip_lines;          /* of every file */
+    int32_t n_fields;
+    int32_t max_rows;            /* the outputs' size: a bound of the batch's rows */
+    int32_t n_columns;
+    uint8_t delimiter;
+    uint8_t pad_[3];
+    gtf_csv_column columns[GTF_CSV_MAX_COLUMNS];
+} gtf_csv_in_ev;
+
+/* Scratch of gtf_csv_parse_ev for a text whose last file ends at total_bytes: positive for 0,
+ * non-decreasing in both; about 8 bytes per chunk and 40 per file. */
+size_t gtf_csv_parse_ev_workspace_bytes(int64_t total_bytes, int32_t n_files);
+
+/* The launches of gtf_csv_parse, one launch and one scan over the files between its scan and its
+ * parse, one upload of the table; no atomic but a file's error word's and first-error key's on a
+ * violation, nothing allocated on the device. Synchronises `stream` once, to fill counts[]. Returns
+ * -2 when any file has an error, the message naming the first such file; -3 for another ABI; -2,
+ * decided on the host before any launch, for what gtf_csv_parse refuses and for a negative
+ * n_files or size, a null table or counts with n_files > 0, a start that is negative, not a
+ * multiple of the chunk or in front of the previous file's end. n_files == 0 or no bytes at all:
+ * returns 0 with zero counts, row_off (if given) zeroed, no workspace needed. */
+int gtf_csv_parse_ev(const gtf_csv_in_ev* in, gtf_csv_counts* counts, void* workspace, size_t workspace_bytes,
+                     gtf_stream_t stream);
+
 /* ---- parsed node columns -> the columns of gtf_event_cols: gtf_event_window -------------
  * gtf/io.py read_nodes after the parse (helper.py:524-531): the rows with lo <= layer_id <= hi,
  * both ends inclusive, compacted in file order, and r = sqrt(x*x + y*y) in fp64.
@@ -1520,6 +1582,21 @@ size_t gtf_event_window_workspace_bytes(int32_t n_rows);
  * before any launch. n_rows == 0: returns 0 with zero counts, nothing launched. */
 int gtf_event_window(const gtf_window_in* in, const gtf_window_out* out, gtf_window_counts* counts,
                      void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* gtf_event_window on a batch's rows: row_off is HOST memory, [n_events + 1], from 0 to
+ * in->n_rows without decreasing (gtf_csv_parse_ev's offsets); one window for the batch. The kept
+ * rows of all events are compacted end to end in batch order, so event e's are the n_kept[e]
+ * behind those of the events in front of it; amb_index holds positions among the batch's kept rows
+ * and gtf_event_radius_patch takes it as it is. The two launches and the exclusive sum of
+ * gtf_event_window and one small gather of the sum at the offsets; one synchronisation, which
+ * fills n_kept (HOST, [n_events]) and counts (the batch's totals). workspace:
+ * gtf_event_window_ev_workspace_bytes. Refusals as gtf_event_window, and -2 for a negative
+ * n_events, null row_off or n_kept with n_events > 0, or offsets that do not start at 0, decrease
+ * or do not end at n_rows. */
+size_t gtf_event_window_ev_workspace_bytes(int32_t n_rows, int32_t n_events);
+int gtf_event_window_ev(const gtf_window_in* in, const int32_t* row_off, int32_t n_events,
+                        const gtf_window_out* out, int32_t* n_kept, gtf_window_counts* counts, void* workspace,
+                        size_t workspace_bytes, gtf_stream_t stream);
 
 /* r[index[k]] = value[k] for k < n; an index outside [0, n_nodes) writes nothing. One launch, does
  * not synchronise. -2 for negative sizes or a null array with n > 0. */
