@@ -336,6 +336,20 @@ class GtfSplitOut(ctypes.Structure):
     _fields_ = [("cand_first", P), ("rem_first", P), ("frag_first", P), ("counts", P), ("cand_ptr_ev", P)]
 
 
+class GtfEventErrorsIo(ctypes.Structure):
+    """gtf_event_errors_io: node_err per event; keyword construction only -- struct_size / abi_version
+    are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("node_err", P), ("event", P), ("node_id", P),
+                ("n_nodes", I32), ("n_events", I32), ("mask", U32), ("pad_", U32), ("err_ev", P), ("n_raising", P),
+                ("first_node", P), ("first_id", P), ("keep", P), ("host_err_ev", P), ("host_n_raising", P),
+                ("host_first_node", P), ("host_first_id", P)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.struct_size = ctypes.sizeof(GtfEventErrorsIo)
+        self.abi_version = ABI_VERSION
+
+
 CSV_MAX_COLUMNS, CSV_MAX_FIELDS, CSV_MAX_ROW_BYTES = 16, 64, 1024   # GTF_CSV_MAX_*
 CSV_INT64, CSV_DOUBLE = 0, 1                                        # GTF_CSV_INT64 / _DOUBLE
 # GTF_CSV_ERR_*
@@ -473,6 +487,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_candidate_order_device_ev",
            "gtf_graph_concat_workspace_bytes", "gtf_graph_concat", "gtf_concat_columns",
            "gtf_event_split_workspace_bytes", "gtf_event_split",
+           "gtf_event_errors_workspace_bytes", "gtf_event_errors",
            "gtf_extract_outputs_workspace_bytes", "gtf_extract_outputs",
            "gtf_score_reset", "gtf_score_workspace_bytes", "gtf_score_candidates",
            "gtf_score_finish_workspace_bytes", "gtf_score_finish",
@@ -572,6 +587,9 @@ def lib(lean: bool = False):
     L.gtf_event_split_workspace_bytes.argtypes = [I32]
     L.gtf_event_split.argtypes = [P, I32, I32, ctypes.POINTER(GtfExtractOutCounts), ctypes.POINTER(GtfSplitIn),
                                   ctypes.POINTER(GtfSplitOut), P, ctypes.c_size_t, P]
+    L.gtf_event_errors_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_event_errors_workspace_bytes.argtypes = [I32]
+    L.gtf_event_errors.argtypes = [ctypes.POINTER(GtfEventErrorsIo), P, ctypes.c_size_t, P]
     L.gtf_extract_outputs_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_extract_outputs_workspace_bytes.argtypes = [I32, I32]
     L.gtf_extract_outputs.argtypes = [G, ctypes.POINTER(GtfExtractIO), I32, P, ctypes.POINTER(GtfExtractOut), P,
@@ -697,7 +715,7 @@ def lib(lean: bool = False):
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
                "gtf_event_split", "gtf_build_events_csr_device", "gtf_truth_concat", "gtf_score_reset_ev",
                "gtf_score_candidates_ev", "gtf_score_finish_ev", "gtf_truth_build_ev", "gtf_csv_parse_ev",
-               "gtf_event_window_ev"):
+               "gtf_event_window_ev", "gtf_event_errors"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

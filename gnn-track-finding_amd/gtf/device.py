@@ -801,6 +801,53 @@ class DeviceGraph:
         for k, v in getattr(self, "diag_t", {}).items():
             v.fill_(float("nan") if k == "edge_chi2" else 0)
 
+    def track_node_errors(self, on: bool = True):
+        """Register a zeroed per-node error array (gtf_diag.node_err, uint32 [N]) ALONE through
+        gtf_set_diagnostics: from now on every reference exception the stage kernels reproduce also ORs its
+        GTF_ERR_* bits into the raising node's entry, which event_errors() reduces per event. The array
+        comes from this graph's own allocator (mem "torch" or "hip": the CLIs never import torch); its zero
+        fill is the whole cost while nothing raises. It replaces whatever set_diagnostics() registered;
+        on=False unregisters it. The registration lives in this graph's workspace: a subset() child starts
+        without one. Natural layout only (the entries are in device node order)."""
+        if on and self.layout != "natural":
+            raise NotImplementedError("track_node_errors: only layout='natural'")
+        self.diag_t = {}
+        self.node_err_t = self._dev_zeros(max(self.n_nodes, 1), np.int32) if on else None
+        d = nat.GtfDiag(ctypes.c_void_p(self.node_err_t.data_ptr() if on else 0), ctypes.c_void_p(0), ctypes.c_void_p(0))
+        nat.check(self.lib.gtf_set_diagnostics(self.ptr("ws"), ctypes.byref(d), self.stream))
+        return self
+
+    def event_errors(self, mask: int = 0xFFFFFFFF, n_events: int = None) -> dict:
+        """gtf_event_errors on the array of track_node_errors() and ``carried["event"]`` (one event without
+        that column): which events raised. Returns the host arrays err_ev [K] uint32, n_raising [K] int32,
+        first_node [K] int32 (-1: none), first_id [K] int64 (the resident node_id column; None without it),
+        and ``keep``, a device uint8 [N] of this graph's allocator: 1 on the nodes of the events that did
+        not raise, what subset() takes. One synchronisation. n_events: this graph's ``n_events`` (1 when it
+        is not a batch)."""
+        if getattr(self, "node_err_t", None) is None:
+            raise ValueError("event_errors needs track_node_errors() before the stage")
+        event = getattr(self, "carried", {}).get("event")
+        K = int(n_events if n_events is not None else (getattr(self, "n_events", 1) if event is not None else 1))
+        N = self.n_nodes
+        out = {"err_ev": np.zeros(K, np.uint32), "n_raising": np.zeros(K, np.int32),
+               "first_node": np.full(K, -1, np.int32), "first_id": None}
+        nid = self.t.get("node_id")
+        if nid is not None:
+            out["first_id"] = np.full(K, -1, np.int64)
+        keep = self._dev_empty(N, np.uint8)
+        if N and K:
+            vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)  # noqa: E731
+            hp = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None else 0)  # noqa: E731
+            io = nat.GtfEventErrorsIo(node_err=vp(self.node_err_t), event=vp(event), node_id=vp(nid), n_nodes=N,
+                                      n_events=K, mask=int(mask) & 0xFFFFFFFF, keep=vp(keep),
+                                      host_err_ev=hp(out["err_ev"]), host_n_raising=hp(out["n_raising"]),
+                                      host_first_node=hp(out["first_node"]), host_first_id=hp(out["first_id"]))
+            nb = int(self.lib.gtf_event_errors_workspace_bytes(K))
+            ws = self._dev_empty(nb, np.uint8)
+            nat.check(self.lib.gtf_event_errors(ctypes.byref(io), vp(ws), ctypes.c_size_t(nb), self.stream))
+        out["keep"] = keep
+        return out
+
     def _host_nodes(self, a, fill=0):
         nm = self.order >= 0
         h = np.full(int(nm.sum()), fill, a.dtype)
@@ -881,7 +928,7 @@ class DeviceGraph:
             self.t["node_id"] = self._dev_from(np.ascontiguousarray(self._node_id_host, np.int64))
         return self.t["node_id"]
 
-    def subset(self, keep, gnn=None, carry=None) -> "DeviceGraph":
+    def subset(self, keep, gnn=None, carry=None, keep_fresh: bool = False) -> "DeviceGraph":
         """The graph after removing the nodes whose `keep` is false, built on the device:
         gtf.graph.subset (extract_track_candidates.py:459-467), array for array, by
         gtf_graph_subset_plan / _apply and gtf_subset_gather, with the child's schedules and
@@ -892,7 +939,9 @@ class DeviceGraph:
         their stored xyzr until the next message passing rewrites them. Natural layout only.
         carry: {name: [N, ...] array} of the caller's own node-axis columns (host, or device of
         this graph's allocator), gathered with the payload; the child holds them as device arrays
-        in ``carried``. The resident node_id column (node_id_dev) travels the same way."""
+        in ``carried``. The resident node_id column (node_id_dev) travels the same way.
+        keep_fresh: the child's uts_fresh keeps bit 0 of the parent's instead of 0 -- a cut in the middle of
+        an iteration (run_batch's on_error="isolate"), where the stage's output is still to be saved."""
         if self.layout != "natural" or self.n_pack_waves:
             raise NotImplementedError("DeviceGraph.subset: only layout='natural' without pack=True (the renumbered, "
                                       "padded and packed layouts are not carried over); this graph has layout=%r, "
@@ -961,7 +1010,8 @@ class DeviceGraph:
                 c.t[f] = c._dev_empty(rows * width, dt)
                 if rows:
                     cols.append(nat.GtfColumn(vp(src), c.ptr(f), width * np.dtype(dt).itemsize,
-                                              self.SUBSET_FILL.get(f, nat.COL_COPY) if axis else nat.COL_COPY))
+                                              self.SUBSET_FILL.get(f, nat.COL_COPY)
+                                              if axis and not (keep_fresh and f == "uts_fresh") else nat.COL_COPY))
             if axis == 0 and rows:
                 cols += [nat.GtfColumn(vp(a), vp(b), rb, nat.COL_COPY) for a, b, rb in extra if rb]
             if cols:

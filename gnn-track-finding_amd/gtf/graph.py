@@ -641,6 +641,55 @@ def split_events(g: TrackGraph, event, n_events: int) -> List[TrackGraph]:
     return out
 
 
+def event_errors(node_err, event, n_events: int, mask: int = 0xFFFFFFFF, node_id=None):
+    """Which events of a fused graph raised: the per-node GTF_ERR_* bits ``node_err`` [N] (gtf_diag.node_err)
+    reduced over the node column ``event`` (non-decreasing, values in [0, n_events), as concat writes
+    and subset carries it; None: one event). The definition of gtf_event_errors. Only the bits of
+    ``mask`` count. Returns (err_ev, n_raising, first_node, first_id, keep):
+      err_ev     [K] uint32  the OR of the masked bits over the event's nodes
+      n_raising  [K] int32   how many of its nodes carry a masked bit
+      first_node [K] int32   its lowest raising node index (the fused graph's numbering), or -1
+      first_id   [K] int64   node_id of that node, or -1; None without ``node_id``
+      keep       [N] uint8   1 where the node's event has err_ev == 0
+    ValueError, naming the first offending node, for an event column that decreases or leaves
+    [0, n_events)."""
+    K = int(n_events)
+    node_err = np.asarray(node_err).astype(np.uint32).reshape(-1)
+    N = node_err.size
+    if K < 0:
+        raise ValueError("n_events must not be negative")
+    if event is None:
+        if K != 1 and N:
+            raise ValueError("event=None means one event (n_events == 1)")
+        ev = np.zeros(N, np.int64)
+    else:
+        ev = np.asarray(event, dtype=np.int64).reshape(-1)
+        if ev.shape != (N,):
+            raise ValueError("event must name the event of each of the %d nodes" % N)
+    wrong = (ev < 0) | (ev >= K)
+    wrong[1:] |= ev[1:] < ev[:-1]
+    if wrong.any():
+        v = int(np.flatnonzero(wrong)[0])
+        raise ValueError("event[%d] is outside [0, %d) or below event[%d]: the column must be non-decreasing"
+                         % (v, K, v - 1))
+    bits = node_err & np.uint32(int(mask) & 0xFFFFFFFF)
+    raising = np.flatnonzero(bits)
+    err_ev = np.zeros(K, np.uint32)
+    np.bitwise_or.at(err_ev, ev[raising], bits[raising])
+    n_raising = np.bincount(ev[raising], minlength=K).astype(np.int32)[:K]
+    first_node = np.full(K, -1, np.int32)
+    first_node[ev[raising][::-1]] = raising[::-1]      # (ascending indices written last to first: the lowest stays)
+    first_id = None
+    if node_id is not None:
+        node_id = np.asarray(node_id, np.int64).reshape(-1)
+        if node_id.shape != (N,):
+            raise ValueError("node_id must have one entry per node")
+        first_id = np.full(K, -1, np.int64)
+        first_id[first_node >= 0] = node_id[first_node[first_node >= 0]]
+    keep = (err_ev[ev] == 0).astype(np.uint8)
+    return err_ev, n_raising, first_node, first_id, keep
+
+
 # --------------------------------------------------------------------------
 # subset: the graph a stage saves after removing nodes (extraction)
 # --------------------------------------------------------------------------

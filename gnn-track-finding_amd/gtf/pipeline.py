@@ -61,6 +61,64 @@ class Iteration:
     counts: Optional[dict] = None             # resident="device": gtf_extract_out_counts' six counts
 
 
+ON_ERROR = ("raise", "name", "isolate")
+
+
+@dataclasses.dataclass
+class EventError:
+    """The reference exception that ended one event of a batch (run_batch / build_events_dev with
+    on_error="isolate"): where the loop was and what DeviceGraph.event_errors says of the event."""
+    iteration: int          # 0: event conversion (build_events_dev)
+    stage: str              # the stage string of the iteration's records, or "update"
+    flags: int              # the event's GTF_ERR_* bits
+    messages: List[str]
+    first_node_id: int      # the node id of the event's first raising node
+    n_raising: int          # how many of its nodes raised
+
+
+class BatchRecords(list):
+    """run_batch's list of K record lists; ``errors`` = {event: EventError} of the events cut out"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.errors = {}
+
+
+class BatchError(ValueError):
+    """on_error="name": raise_errors' exception with the failing events; ``events`` = {event: flags}"""
+
+    def __init__(self, msg, events):
+        super().__init__(msg)
+        self.events = events
+
+
+def _check_on_error(on_error):
+    if on_error not in ON_ERROR:
+        raise ValueError("on_error must be 'raise', 'name' or 'isolate'")
+
+
+def _cut_failed(d, K, flags, on_error, iteration, stage, errors):
+    """the error word of d's workspace is ``flags`` != 0: name the raising events (DeviceGraph.event_errors)
+    and, on_error "isolate", record them in ``errors`` and cut them out of d. Returns (the child, the
+    events cut). "name", or bits that no node recorded: raises."""
+    from . import _native as nat
+    messages = lambda f: [m for b, m in nat.ERR_FLAGS.items() if f & b]  # noqa: E731
+    lead = "reference exception reproduced on device: " + "; ".join(messages(flags))
+    r = d.event_errors(n_events=K)
+    failed = [int(e) for e in np.flatnonzero(r["err_ev"])]
+    if flags & ~int(np.bitwise_or.reduce(r["err_ev"], initial=np.uint32(0))):
+        raise ValueError(lead)   # (raised outside the per-node path: no event to name)
+    if on_error == "name":
+        raise BatchError(lead + " -- " + "; ".join("event %d: %s; node id %d" % (
+            e, "; ".join(messages(int(r["err_ev"][e]))), int(r["first_id"][e])) for e in failed),
+            {e: int(r["err_ev"][e]) for e in failed})
+    for e in failed:
+        f = int(r["err_ev"][e])
+        errors[e] = EventError(iteration, stage, f, messages(f), int(r["first_id"][e]), int(r["n_raising"][e]))
+    child = d.subset(r["keep"], carry={"vivl": d.carried["vivl"], "event": d.carried["event"]}, keep_fresh=True)
+    return child, failed
+
+
 def event_layout(event_prefix: str, min_volume: int, max_volume: int, builder: str = "native", device="cuda"):
     """Host half of event conversion: the packed network in the reference's orders,
     with empty track_state_estimates dicts keyed in their set order and every edge
@@ -167,21 +225,39 @@ def _event_columns(event_prefix, min_volume, max_volume, device, mem, parse):
     return (ids, x, y, z, r, layer, n1, n2), info
 
 
-def _event_states(d, p):
+def _event_states(d, p, on_error="raise"):
     """the states, priors, mixture weights, degrees and send weights of a fresh from_event /
-    from_events graph (event_conversion.py:86-101), on that object"""
+    from_events graph (event_conversion.py:86-101), on that object. on_error (a fused graph):
+    build_events_dev's"""
+    if on_error != "raise":
+        d.event_error_records = {}
     if d.n_nodes == 0:
         return d
     d.clear_errors()
+    if on_error != "raise":
+        d.track_node_errors()
     d.track_state_estimates(p)
     d.node_ops(["priors_tse", "mw_tse", "degree"], p)
-    d.raise_errors()
+    if on_error == "raise":
+        d.raise_errors()
+    else:
+        flags = d.errors()
+        if flags:
+            records = {}
+            c, failed = _cut_failed(d, d.n_events, flags, on_error, 0, "event_conversion", records)
+            # the child stands in for the fused graph: whole events left, so no orphan key and the ids
+            # and vivl resident (host_graph); the events cut hold no node
+            c._event, c.parse_info, c.event_error_records = True, getattr(d, "parse_info", None), records
+            c.event_nodes = [0 if e in records else n for e, n in enumerate(d.event_nodes)]
+            d = c
+            if d.n_nodes == 0:
+                return d
     d.refresh_send_mw()
     return d
 
 
 def build_events_dev(prefixes, min_volume: int, max_volume: int, p: Params = None, device="cuda",
-                     mem: str = "torch", parse: str = "host", batch_parse: bool = False):
+                     mem: str = "torch", parse: str = "host", batch_parse: bool = False, on_error: str = "raise"):
     """build_event_dev for a batch of events in ONE build: every event's files are read as
     build_event_dev reads them (the device parse and its per-file host fallback stay per file;
     ``parse_info`` is the list of the events' records), DeviceGraph.from_events makes the fused graph --
@@ -192,9 +268,15 @@ def build_events_dev(prefixes, min_volume: int, max_volume: int, p: Params = Non
     gtf_csv_parse_ev, one gtf_event_window_ev and one radius patch (io.read_nodes_batch_dev), all
     edges.csv in one more parse (io.read_edges_batch_dev) -- and the fused columns go to
     DeviceGraph.from_fused without a gather. The same graph, bit for bit; ``parse_info`` is again one
-    record per event, with "batch": the ParsedBatch infos of the two kinds."""
+    record per event, with "batch": the ParsedBatch infos of the two kinds.
+    on_error: what a reference exception in the states' kernels does, as in run_batch. "raise" (default):
+    DeviceGraph.raise_errors on the fused graph's error word. "name": the same exception as a BatchError
+    that names the failing events. "isolate": the failing events are cut out of the returned graph
+    (their ``event_nodes`` entry is 0, the others' nodes are untouched) and ``d.event_error_records`` =
+    {event: EventError} with iteration 0; it is empty on a clean build."""
     from .device import DeviceGraph
     p = p or Params()
+    _check_on_error(on_error)
     if batch_parse:
         if parse != "device":
             raise ValueError("batch_parse needs parse='device'")
@@ -211,11 +293,11 @@ def build_events_dev(prefixes, min_volume: int, max_volume: int, p: Params = Non
             if ed.reasons[e]:
                 info["edges_reason"] = ed.reasons[e]
             d.parse_info.append(info)
-        return _event_states(d, p)
+        return _event_states(d, p, on_error)
     read = [_event_columns(prefix, min_volume, max_volume, device, mem, parse) for prefix in prefixes]
     d = DeviceGraph.from_events([cols for cols, _ in read], device, mem)
     d.parse_info = [info for _, info in read]
-    return _event_states(d, p)
+    return _event_states(d, p, on_error)
 
 
 def _ids(g: TrackGraph, groups):
@@ -230,7 +312,8 @@ def _dev_slice(d, t, start: int, n: int):
 
 
 def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = None, scorers=None,
-              lists: bool = True, first: int = 1, keep_graphs: bool = False) -> List[List[Iteration]]:
+              lists: bool = True, first: int = 1, keep_graphs: bool = False,
+              on_error: str = "raise") -> List[List[Iteration]]:
     """run(d, None, resident="device") for K resident events at once: ``ds`` (the DeviceGraphs of
     build_event_dev, one allocator and device) are fused by DeviceGraph.concat and the loop runs ONCE on
     the fused graph, so the synchronisations of an iteration -- the connected-components rounds, the
@@ -251,8 +334,22 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
     (what run_pipeline.py saves), cut on the host (graph.split_events) from downloads of the fused
     graphs after each step -- as in run(), a record's remaining_graph ends holding the next stage's
     output and merged coordinates.
-    A reference exception (DeviceGraph.raise_errors) in any event raises here as it does in run(); the
-    error word is the fused graph's, so the message does not say which event.
+    on_error: what a reference exception in one event does to the batch.
+    "raise" (default): DeviceGraph.raise_errors on the fused graph's error word, as run() raises; the
+    word is the batch's, so the message does not say which event, and no record is returned.
+    "name": the same exception as a BatchError whose text goes on with "event e: <its messages>; node id
+    <its first raising node>" for every failing event; ``.events`` = {e: flags}.
+    "isolate": the batch behaves as the per-event loop does. Every stage and update() runs with a per-node
+    error array registered (DeviceGraph.track_node_errors: one zero fill, nothing else while the error
+    word stays 0). When the word is set, gtf_event_errors names the raising events and
+    subset(keep of the others) cuts them out BEFORE candidate order and extraction, so nothing reads a
+    raised event's half-written state; events share no edge, so the child is the fused graph of the
+    survivors, whose records stay those of run() on each alone. A failed event's list ends with its last
+    clean iteration (a failure in the update() after iteration 2 keeps iteration 2's record), scorers see
+    it as an event that ran out of nodes from then on, keep_graphs cuts the host copy in step, and the
+    returned list (a BatchRecords) holds ``errors`` = {e: EventError(iteration, stage, flags, messages,
+    first_node_id, n_raising)}, stage "update" for update(); empty on a clean run. Bits in the error
+    word that no node recorded raise as "raise" does.
     ``ds`` may also be ONE fused graph as build_events_dev returns it (DeviceGraph.from_events: it holds
     ``event_nodes``): the loop starts on it without a concat, the events' node counts are its
     ``event_nodes`` and keep_graphs takes its own host_graph(). The same records; iteration ``first``
@@ -260,6 +357,8 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
     from .device import DeviceGraph
     p = p or Params()
     ex = ex or extract.Params()
+    _check_on_error(on_error)
+    track = on_error != "raise"
     fused = ds if isinstance(ds, DeviceGraph) else None
     if fused is not None and not hasattr(fused, "event_nodes"):
         raise ValueError("run_batch takes a list of resident events or one fused graph of build_events_dev")
@@ -275,7 +374,7 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
             raise ValueError("run_batch takes resident events (the DeviceGraphs of build_event_dev)")
         if "node_id" not in g.t or "vivl" not in getattr(g, "carried", {}):
             raise ValueError("a DeviceGraph input must hold the node_id and vivl columns (DeviceGraph.from_event)")
-    out = [[] for _ in range(K)]
+    out = BatchRecords([] for _ in range(K))   # (a list of K lists; .errors stays empty unless on_error="isolate" cuts)
     if K == 0:
         return out
     t0 = time.perf_counter()
@@ -294,6 +393,8 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
             t0 = time.perf_counter()
         torch = d.torch
         d.clear_errors()
+        if track:
+            d.track_node_errors()
         if it == 1:
             stage = "clustering(track_state_estimates)"
             d.cluster("tse", CLUSTER_FIRST[0], CLUSTER_FIRST[1], p)
@@ -303,7 +404,18 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
         else:
             stage = "clustering(updated_track_states)"
             d.cluster("uts", CLUSTER_LATER[0], CLUSTER_LATER[1], p)
-        d.raise_errors()
+        if not track:
+            d.raise_errors()
+        else:
+            flags = d.errors()
+            if flags:   # the raising events leave before anything reads the stage's output
+                d, failed = _cut_failed(d, K, flags, on_error, it, stage, out.errors)
+                for e in failed:
+                    left[e] = 0
+                if keep_graphs:
+                    G = d.to_host(G)
+                if d.n_nodes == 0:
+                    break
         if torch is not None:
             torch.cuda.synchronize(d.device)
         t1 = time.perf_counter()
@@ -335,10 +447,16 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
                  for k in ("pval_xy", "pval_zr")}
         dnext = d.subset(o["keep"], gnn=res["gnn"], carry={"vivl": vivl_dev, "event": event_dev})
         dnext.refresh_send_mw()
+        update_flags = 0
         if it % 2 == 0 and dnext.n_nodes:      # remove_state_metadata.py, as in run()
             dnext.clear_errors()
+            if track:
+                dnext.track_node_errors()
             dnext.update(p)
-            dnext.raise_errors()
+            if track:
+                update_flags = dnext.errors()
+            else:
+                dnext.raise_errors()
         t3 = time.perf_counter()
         seconds = {"stage": t1 - t0, "extract": t2 - t1, "next": t3 - t2}
         if keep_graphs:   # after the step (it left d's arrays as the stage wrote them), as in run()
@@ -365,6 +483,12 @@ def run_batch(ds, iterations: int = 3, p: Params = None, ex: extract.Params = No
                 rec = out[e][-1]
                 rec.network, rec.remaining_graph, rec.remaining_vivl = nets[e], rems[e], vivl2[cut[e]:cut[e + 1]]
             left[e] = sp["counts"][e]["n_remaining_nodes"]
+        if update_flags:   # update() raised: this iteration's records stand, the raising events end here
+            dnext, failed = _cut_failed(dnext, K, update_flags, on_error, it, "update", out.errors)
+            for e in failed:
+                left[e] = 0
+            if keep_graphs:
+                G = dnext.to_host(G)
         d = dnext
     return out
 

@@ -34,7 +34,11 @@ the device parser's exact domain is read by the host reader. The same files eith
 (pipeline.run_batch); with --truth (one directory for every event, or one per event) the candidates are
 scored on the GPU as with --resident-metrics. Event i's files go under ROOTDIR/<i>/ in the layout above, the
 same files a single run of that event writes. If a stage raises a reference exception the whole batch
-stops; the message does not say which event.
+stops (--batch-on-error raise, the default; name: the message names the failing events). With
+--batch-on-error isolate the failing events are cut out of the fused graph (pipeline.run_batch(on_error=
+"isolate")): ROOTDIR/<i>/ of a failed event holds its clean iterations and error.json (iteration, stage,
+flags, messages, node_id, n_raising) and no metrics.json, one line says so, the other events' files are
+those of the same command without the failing directories, and the exit status is 0.
 --batch-build (with --batch) builds the events in ONE call (pipeline.build_events_dev:
 gtf_build_events_csr_device on the concatenated columns) instead of once per event followed by the concat:
 the same files under ROOTDIR/<i>/.
@@ -222,6 +226,11 @@ def main(argv=None):
     ap.add_argument("--batch-build", action="store_true",
                     help="with --batch: one graph build for all events (pipeline.build_events_dev) instead of one "
                          "per event and a concat; the same files")
+    ap.add_argument("--batch-on-error", choices=("raise", "name", "isolate"), default="raise",
+                    help="with --batch: what a reference exception in one event does (pipeline.run_batch(on_error=)): "
+                         "raise: the whole batch stops, as before; name: it stops and the message names the failing "
+                         "events; isolate: the failing events are cut out, their ROOTDIR/<i>/ holds their clean "
+                         "iterations and an error.json (no metrics.json), the others finish and the exit status is 0")
     ap.add_argument("--batch-metrics", action="store_true",
                     help="with --batch and --truth: one pair of scorers for the whole batch (gtf.metrics.BatchScorer: "
                          "one scoring call per iteration) instead of a pair per event; the same metrics.json files")
@@ -251,6 +260,8 @@ def main(argv=None):
             ap.error("--batch names the event directories itself: not with -n")
     if args.batch_build and not args.batch:
         ap.error("--batch-build builds the events of --batch")
+    if args.batch_on_error != "raise" and not args.batch:
+        ap.error("--batch-on-error is a policy of --batch")
     if args.batch_metrics and not (args.batch and args.truth_dirs):
         ap.error("--batch-metrics scores the events of --batch against --truth")
     if args.batch_truth and not args.batch_metrics:
@@ -358,7 +369,7 @@ def _batch(args, p, ex):
         fused = pipeline.build_events_dev([os.path.join(dn, "event_1_filtered_graph_") for dn in args.batch],
                                           args.min_volume, args.max_volume, p, args.device,
                                           parse="device" if args.resident_parse else "host",
-                                          batch_parse=args.batch_parse)
+                                          batch_parse=args.batch_parse, on_error=args.batch_on_error)
         if args.resident_parse:
             for info in fused.parse_info:
                 for key in ("nodes", "edges"):
@@ -395,16 +406,27 @@ def _batch(args, p, ex):
             batch = _BatchScorers(_tables_batch(args, truth), args.device)
         else:
             batch = _BatchScorers([_tables(args, t) if t else None for t in truth], args.device)
-        its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=batch, first=1, keep_graphs=True)
+        its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=batch, first=1, keep_graphs=True,
+                                 on_error=args.batch_on_error)
         scorers = batch.per_event()
     else:
         scorers = [_scorers(args, t) if t else None for t in truth]
         its = pipeline.run_batch(devs, args.end - args.start + 1, p, ex, scorers=scorers if args.truth_dirs else None,
-                                 first=1, keep_graphs=True)
+                                 first=1, keep_graphs=True, on_error=args.batch_on_error)
+    errors = dict(getattr(devs, "event_error_records", None) or {})   # (--batch-build: raised in the conversion)
+    errors.update(getattr(its, "errors", {}))
     for i, rec in enumerate(its):
         root = os.path.join(args.outputDir, str(i))
         print("event %d:" % i)
         _save(root, rec, times[i])
+        if i in errors:   # --batch-on-error isolate: its clean iterations above, no metrics
+            err = errors[i]
+            with open(os.path.join(root, "error.json"), "w") as f:
+                json.dump({"iteration": err.iteration, "stage": err.stage, "flags": err.flags, "messages": err.messages,
+                           "node_id": err.first_node_id, "n_raising": err.n_raising}, f, indent=1)
+            print("event %d failed in iteration %d (%s): %s; node id %d"
+                  % (i, err.iteration, err.stage, "; ".join(err.messages), err.first_node_id))
+            continue
         _metrics(args, root, rec, scorers[i], truth[i])
     return 0
 

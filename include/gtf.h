@@ -1882,6 +1882,65 @@ int gtf_event_split(const int32_t* event, int32_t n_nodes, int32_t n_events,
                     const gtf_extract_out_counts* counts, const gtf_split_in* in, const gtf_split_out* out,
                     void* workspace, size_t workspace_bytes, gtf_stream_t stream);
 
+/* ---- Which event of a batch raised: gtf_diag.node_err per event (csrc/gtf_event_errors.hip) ----
+ * The error word of a fused graph's workspace says that a reference exception was reproduced,
+ * not in which event. With node_err registered (gtf_set_diagnostics) the pass kernels also OR
+ * the GTF_ERR_* bits into the raising node's entry; this call reduces that array over the
+ * event column that gtf_graph_concat writes and gtf_subset_gather carries, and makes the keep
+ * mask that cuts the raising events out (gtf_graph_subset_plan).
+ * Inputs, DEVICE arrays:
+ *   node_err [n_nodes] uint32   the per-node bits
+ *   event    [n_nodes] int32    non-decreasing, values in [0, n_events); NULL: one event
+ *                               (n_events must then be 1)
+ *   node_id  [n_nodes] int64    or NULL
+ *   mask                        the bits that count; the others are ignored
+ * Outputs, DEVICE arrays, each may be NULL; the call overwrites every entry of every one given
+ * (the caller does not zero them):
+ *   err_ev     [n_events] uint32  the OR of the masked bits over the event's nodes
+ *   n_raising  [n_events] int32   how many of the event's nodes carry a masked bit
+ *   first_node [n_events] int32   the lowest raising node index of the event, in the fused
+ *                                 graph's numbering, or -1
+ *   first_id   [n_events] int64   node_id[first_node], or -1 for an event without a raising
+ *                                 node; written only when node_id is given
+ *   keep       [n_nodes]  uint8   1 where the node's event has err_ev == 0
+ * host_err_ev, host_n_raising, host_first_node, host_first_id: HOST arrays of the same sizes,
+ * each may be NULL, filled from one copy after the call's ONE synchronisation (host_first_id
+ * only when node_id is given).
+ * Three launches whatever n_events is (initialise, reduce, write out). A node without a masked
+ * bit issues no atomic; a raising node issues three on its event's entries. The kernels check
+ * what the reduction relies on: event[v] in [0, n_events) and event[v - 1] <= event[v]. A node
+ * that breaks either is recorded (the lowest such index, an atomic only on the violation),
+ * one whose event is out of range contributes nothing and gets keep 0; the call then returns
+ * -2 and gtf_last_error() names that node; the outputs hold nothing to rely on, but every
+ * write stayed inside them.
+ * Returns 0; -2 also on the host, before any launch: negative sizes, a missing node_err with
+ * nodes, event == NULL with n_events != 1, a workspace below
+ * gtf_event_errors_workspace_bytes(n_events); -3: *io built against another layout of this
+ * header (struct_size, abi_version). n_nodes == 0 or n_events == 0: returns 0, nothing is
+ * launched and nothing written. */
+typedef struct gtf_event_errors_io {
+    uint32_t struct_size;        /* sizeof(gtf_event_errors_io) as the caller compiled it */
+    uint32_t abi_version;        /* GTF_ABI_VERSION */
+    const uint32_t* node_err;
+    const int32_t* event;
+    const int64_t* node_id;
+    int32_t n_nodes, n_events;
+    uint32_t mask;
+    uint32_t pad_;
+    uint32_t* err_ev;
+    int32_t* n_raising;
+    int32_t* first_node;
+    int64_t* first_id;
+    uint8_t* keep;
+    uint32_t* host_err_ev;
+    int32_t* host_n_raising;
+    int32_t* host_first_node;
+    int64_t* host_first_id;
+} gtf_event_errors_io;
+
+size_t gtf_event_errors_workspace_bytes(int32_t n_events);
+int gtf_event_errors(const gtf_event_errors_io* io, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
 /* Member order of every extraction candidate as the reference builds it: CCA over the
  * active edges of each subgraph (extract_track_candidates.py:332-346) -- networkx
  * weakly connected components, each copied as subGraph.subgraph(component) (set order
