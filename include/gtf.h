@@ -238,11 +238,11 @@ typedef struct gtf_params {
 /* Device-detected reference exceptions (bit flags in the error word). */
 enum {
     GTF_ERR_SEND_MW_MISSING = 1,   /* KeyError extrapolate_merged_states.py:384 */
-    GTF_ERR_STALE_KEY_NO_EDGE = 2, /* KeyError helper.py:131/138 */
-    GTF_ERR_ALL_ZERO_DIST = 4,     /* ValueError clustering.py:120 (np.min of empty) */
+    GTF_ERR_STALE_KEY_NO_EDGE = 2, /* KeyError helper.py:131/138; the node's reweight goes on with lr_layer_norm = 1 for its active keys */
+    GTF_ERR_ALL_ZERO_DIST = 4,     /* ValueError clustering.py:120 (np.min of empty); the node is left as it was: no merged state, no edge deactivated */
     GTF_ERR_TIE_EMPTIED = 8,       /* ValueError clustering.py:116 (tie removed every state) */
-    GTF_ERR_EMPTY_DICT_MW = 16,    /* ZeroDivisionError helper.py:90 */
-    GTF_ERR_NAN_KL = 32,           /* ValueError clustering.py:117 (list.index of NaN) */
+    GTF_ERR_EMPTY_DICT_MW = 16,    /* ZeroDivisionError helper.py:90; nothing is written for the node */
+    GTF_ERR_NAN_KL = 32,           /* ValueError clustering.py:117 (list.index of NaN); the merged state formed so far is stored and the keys still in the list are deactivated */
     GTF_ERR_NO_STATE_DICT = 64,    /* KeyError remove_state_metadata.py:39 */
     GTF_ERR_SINGULAR_H = 128,      /* LinAlgError learn_KL_parabolic_model/.../utils.py:277 (x_B = 0 or x_B = x_0) */
     GTF_ERR_PAIR_COUNT = 256,      /* pair_ptr disagrees with the state dicts (caller error, a15) */

@@ -281,7 +281,7 @@ def reweight(g: TrackGraph, pfx: str = "uts", threshold: float = 0.1) -> None:
                     right.append(k); rc.append(nx_)
         last = order[-1] if order else None           # stale loop variable (helper.py:131,138)
         if (left or right) and not S["is_edge"][last]:
-            raise ReferenceError_("KeyError: stale neighbour_num has no edge (helper.py:131)")
+            raise ReferenceError_("KeyError: stale neighbour_num has no edge (helper.py:%d)" % (131 if left else 138))
         left_norm = len(list(set(lc)))
         for k in left:
             S["uts_side"][k] = 0
@@ -471,6 +471,8 @@ def merge_states(mean1, cov1, mean2, cov2):                                     
 def get_smallest_dist_idx(distances):                                            # clustering.py:114-124
     if isinstance(distances, list):
         smallest = np.min(distances)
+        if np.isnan(smallest):                     # list.index never finds a NaN (:117)
+            raise ReferenceError_("ValueError: NaN KL distance is not in the list (clustering.py:117)")
         return smallest, distances.index(smallest)
     nonzero = distances[np.nonzero(distances)]
     smallest = np.min(nonzero)

@@ -71,7 +71,7 @@ def compare(got, exp, rtol=1e-6, atol=1e-12, fields=None, report=8):
     for f in FLOAT_NODE:
         if use(f):
             ok = _close(got.node[f], exp.node[f], rtol, atol)
-            ok = ok.reshape(ok.shape[0], -1).all(axis=1) | ~mm
+            ok = ok.reshape(ok.shape[0], -1 if ok.size else 1).all(axis=1) | ~mm
             bad = np.nonzero(~ok)[0]
             if bad.size:
                 errs.append("node.%s: %d mismatches, e.g. node %d got %s exp %s" % (
@@ -81,7 +81,7 @@ def compare(got, exp, rtol=1e-6, atol=1e-12, fields=None, report=8):
         for f in flist:
             if use(f):
                 ok = _close(got.slot[f], exp.slot[f], rtol, atol)
-                ok = ok.reshape(ok.shape[0], -1).all(axis=1) | ~present
+                ok = ok.reshape(ok.shape[0], -1 if ok.size else 1).all(axis=1) | ~present   # (a graph without slots)
                 bad = np.nonzero(~ok)[0]
                 if bad.size:
                     errs.append("slot.%s: %d mismatches, e.g. slot %d got %s exp %s" % (

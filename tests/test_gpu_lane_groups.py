@@ -19,6 +19,7 @@ from compare import compare, compare_noise, noise_envelope
 from fixtures import load
 from gtf import graph, synth
 from gtf.params import Params
+from pass_cases import distances as _tse_distances, tied as _tied   # (the pairwise chi2 matrix of a node's dict)
 
 pytestmark = pytest.mark.gpu
 
@@ -169,26 +170,6 @@ def test_exact_counts(counts):
         _, got0, flags0 = _gpu(g, _passes(p, 1), None, groups=False, layout=layout)
         assert flags0 == 0
         _bit_equal(got, got0, layout)
-
-
-def _tse_distances(g, v, p):
-    """the pairwise chi2 matrix of node v's track-state estimates (clustering.py:80-86)"""
-    S = g.slot
-    order = O._dict_order(g, "tse", v)
-    jsv = np.array([[S["tse_sv"][k][0], S["tse_sv"][k][1], S["tse_tau"][k]] for k in order])
-    jcov = np.array([O.mat_from_cov5(S["tse_cov"][k]) for k in order])
-    xyzr = np.array([S["tse_xyzr"][k] for k in order])
-    D = np.zeros((len(order), len(order)))
-    for i in range(len(order)):
-        for j in range(i):
-            D[i][j] = O.mahalanobis_distance(jsv[i], jcov[i], jsv[j], jcov[j], g.node["xyzr"][v], xyzr[i], xyzr[j],
-                                             p.sigma0rz, p.sigma0rz2, p.endcap_boundary)
-    return order, D
-
-
-def _tied(D):
-    nz = D[np.nonzero(D)]
-    return nz.size > 0 and int((D == nz.min()).sum()) >= 2
 
 
 def _params(meta):
