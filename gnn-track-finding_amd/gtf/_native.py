@@ -460,6 +460,34 @@ class GtfKlOut32(ctypes.Structure):
     _fields_ = [("kl", P), ("truth", P), ("emp_var", P), ("emp_mean", P), ("err", P)]
 
 
+class GtfKlPrepareIn(ctypes.Structure):
+    """gtf_kl_prepare_in: what gtf_kl_prepare reads, device arrays; keyword construction only --
+    struct_size / abi_version are filled in (another layout: status -3)"""
+    _fields_ = [("struct_size", U32), ("abi_version", U32), ("n_nodes", I32), ("n_slots", I32), ("slot_ptr", P),
+                ("slot_src", P), ("is_edge", P), ("gnn", P), ("truth", P), ("gnn_stride", I32), ("with_single", I32),
+                ("layout", I32), ("compact", I32), ("scale", ctypes.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(GtfKlPrepareIn)
+        self.abi_version = ABI_VERSION
+
+
+class GtfKlPrepareBuf(ctypes.Structure):
+    """gtf_kl_prepare_buf: the caller-allocated outputs of gtf_kl_prepare"""
+    _fields_ = [("slot_ptr", P), ("slot_src", P), ("xy", P), ("truth", P), ("pair_ptr", P), ("list", P),
+                ("node_of", P), ("slot_of", P), ("q", P), ("truth32", P)]
+
+
+class GtfKlCounts(ctypes.Structure):
+    _fields_ = [("n_kept", I32), ("n_listed", I32), ("n_pairs", ctypes.c_int64), ("count", I32 * 4),
+                ("first", I32 * 4), ("n_d1", I32), ("n_deg", I32 * 6), ("error", U32), ("scale", ctypes.c_double),
+                ("max_abs", ctypes.c_double)]
+
+
+KL_ERR_SLOT_PTR, KL_ERR_SOURCE, KL_ERR_NONFINITE, KL_ERR_FIT, KL_ERR_SCALE, KL_ERR_NODE_OF = 1, 2, 4, 8, 16, 32
+
+
 GTF_F64, GTF_F32 = 0, 1
 
 ERR_FLAGS = {
@@ -496,6 +524,7 @@ SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "
            "gtf_score_finish_ev_workspace_bytes", "gtf_score_finish_ev",
            "gtf_truth_build_workspace_bytes", "gtf_truth_build",
            "gtf_truth_build_ev_workspace_bytes", "gtf_truth_build_ev",
+           "gtf_kl_prepare_workspace_bytes", "gtf_kl_prepare", "gtf_kl_coords", "gtf_kl_pair_rows",
            "gtf_build_event_device_workspace_bytes", "gtf_build_event_csr_device",
            "gtf_build_events_device_workspace_bytes", "gtf_build_events_csr_device",
            "gtf_graph_prepare_workspace_bytes", "gtf_graph_prepare",
@@ -636,6 +665,13 @@ def lib(lean: bool = False):
     L.gtf_parabolic_kl.argtypes = [ctypes.POINTER(GtfKlGraph), I32, ctypes.POINTER(GtfKlOut), P]
     L.gtf_parabolic_kl_q32.argtypes = [ctypes.POINTER(GtfKlGraph), ctypes.POINTER(GtfKlQ32),
                                        ctypes.POINTER(GtfKlOut32), P]
+    L.gtf_kl_prepare_workspace_bytes.restype = ctypes.c_size_t
+    L.gtf_kl_prepare_workspace_bytes.argtypes = [I32, I32]
+    L.gtf_kl_prepare.argtypes = [ctypes.POINTER(GtfKlPrepareIn), ctypes.POINTER(GtfKlPrepareBuf),
+                                 ctypes.POINTER(GtfKlGraph), ctypes.POINTER(GtfKlQ32), ctypes.POINTER(GtfKlCounts), P,
+                                 ctypes.c_size_t, P]
+    L.gtf_kl_coords.argtypes = [I32, P, I32, P, P, P, F64, P, P]
+    L.gtf_kl_pair_rows.argtypes = [ctypes.POINTER(GtfKlGraph), ctypes.c_int64, P, P, I32, P, P, P, P, P]
     L.gtf_build_event_csr.argtypes = [ctypes.POINTER(GtfEventCsr)]
     L.gtf_build_event_device_workspace_bytes.restype = ctypes.c_size_t
     L.gtf_build_event_device_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -715,7 +751,7 @@ def lib(lean: bool = False):
                "gtf_event_radius_patch", "gtf_candidate_order_device_ev", "gtf_graph_concat", "gtf_concat_columns",
                "gtf_event_split", "gtf_build_events_csr_device", "gtf_truth_concat", "gtf_score_reset_ev",
                "gtf_score_candidates_ev", "gtf_score_finish_ev", "gtf_truth_build_ev", "gtf_csv_parse_ev",
-               "gtf_event_window_ev", "gtf_event_errors"):
+               "gtf_event_window_ev", "gtf_event_errors", "gtf_kl_prepare", "gtf_kl_coords", "gtf_kl_pair_rows"):
         getattr(L, fn).restype = ctypes.c_int
     _lib = L
     return L

@@ -75,6 +75,43 @@ def in_edge_csr(g: TrackGraph):
     return ptr, g.slot["slot_src"][ise].astype(np.int32)
 
 
+def _down(t):
+    return t.cpu().numpy() if t is not None else None
+
+
+def _lazy(name, fetch):
+    """an attribute that is either assigned or, on its first read, fetched and kept"""
+    key = "_lazy_" + name
+
+    def fget(self):
+        if key not in self.__dict__:
+            self.__dict__[key] = fetch(self)
+        return self.__dict__[key]
+
+    def fset(self, v):
+        self.__dict__[key] = v
+    return property(fget, fset)
+
+
+def _raise_prepare_error(c):
+    """the ValueError of a gtf_kl_prepare / gtf_kl_coords error word (quantise_xy's wording for its rules)"""
+    e = int(c.error) if hasattr(c, "error") else int(c)
+    if e & (nat.KL_ERR_SLOT_PTR | nat.KL_ERR_SOURCE | nat.KL_ERR_NODE_OF):
+        raise ValueError("ParabolicKL: " + ("slot_ptr does not start at 0, decreases or does not end at n_slots"
+                                            if e & nat.KL_ERR_SLOT_PTR else
+                                            "a kept slot's source outside [0, n_nodes)" if e & nat.KL_ERR_SOURCE
+                                            else "a node_of entry outside [0, n_nodes)"))
+    if e & nat.KL_ERR_NONFINITE:
+        raise ValueError("quantise_xy: non-finite coordinate")
+    if e & nat.KL_ERR_SCALE:
+        raise ValueError("quantise_xy: scale must be finite and > 0")
+    if e & nat.KL_ERR_FIT:
+        if hasattr(c, "max_abs"):
+            raise ValueError("quantise_xy: max |x|, |y| = %g does not fit scale %g (|q| < 2^30)" % (c.max_abs, c.scale))
+        raise ValueError("quantise_xy: the coordinates do not fit the scale (|q| < 2^30)")
+    raise ValueError("ParabolicKL: device error word %d" % e)
+
+
 class ParabolicKL:
     """Device-resident KL graph of one or many events (events concatenated into one CSR).
 
@@ -97,10 +134,39 @@ class ParabolicKL:
     their scale, and the truth ids as int32 (ids beyond int32 relabelled densely: only their
     equality matters), for run(out, "q32") -- gtf_parabolic_kl_q32, 12
     bytes per node instead of 24, fp32 arithmetic. The structure arrays are shared with the
-    fp64 path; without compact the object and its device footprint are unchanged."""
+    fp64 path; without compact the object and its device footprint are unchanged.
+
+    prepare "host" (default): everything above is built in NumPy and uploaded; this is the
+    definition. prepare "device": the caller's raw arrays are uploaded and gtf_kl_prepare
+    (include/gtf.h) builds the same arrays in HBM, element for element; from_device and
+    from_device_graph do so on arrays that are resident already. node_of, slot_of, degree,
+    slot_ptr_host and pair_ptr_host are then downloaded on first use, and in the ordered layout
+    ``lists`` is empty (the kernel reads ranges, no list). Not with tile > 0."""
+
+    # host copies of the structure: set by the host constructor; after prepare="device" each is
+    # downloaded on its first use (pair_index, host_nodes and host_slots read them)
+    node_of = _lazy("node_of", lambda k: _down(k._node_of_dev))
+    slot_of = _lazy("slot_of", lambda k: _down(k._slot_of_dev))
+    slot_ptr_host = _lazy("slot_ptr_host", lambda k: k.slot_ptr.cpu().numpy().astype(np.int64))
+    pair_ptr_host = _lazy("pair_ptr_host", lambda k: k.pair_ptr.cpu().numpy())
+    degree = _lazy("degree", lambda k: np.diff(k.slot_ptr_host))
 
     def __init__(self, slot_ptr, slot_src, gnn, truth=None, device="cuda", with_single=False, ordered=False,
-                 tile=0, sort_window=8192, tile_b1=True, compact=False):
+                 tile=0, sort_window=8192, tile_b1=True, compact=False, prepare="host"):
+        if prepare not in ("host", "device"):
+            raise ValueError("prepare must be 'host' or 'device'")
+        if prepare == "device":   # the caller's raw arrays go up; gtf_kl_prepare builds the rest
+            if int(tile) > 0:
+                raise ValueError("prepare='device' does not build the tiled layout (its node order sorts by "
+                                 "np.arctan2, which a device atan2 does not reproduce bit for bit): use prepare='host'")
+            dev = torch.device(device)
+            t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)  # noqa: E731
+            g = np.asarray(gnn, np.float64)
+            g = g.reshape(-1, g.shape[-1] if g.ndim > 1 else 4)
+            self._prepare_device(t(slot_ptr, np.int32).reshape(-1), t(slot_src, np.int32).reshape(-1), t(g, np.float64),
+                                 t(truth, np.int64).reshape(-1) if truth is not None else None, None, with_single,
+                                 ordered, compact, None)
+            return
         slot_ptr = np.ascontiguousarray(slot_ptr, np.int32)
         self.n_nodes = int(slot_ptr.shape[0] - 1)
         self.n_slots = int(slot_ptr[-1])
@@ -211,6 +277,125 @@ class ParabolicKL:
             self.truth32 = torch.from_numpy(np.ascontiguousarray(t64.astype(np.int32))).to(self.device)
         self._q = nat.GtfKlQ32(_ptr(self.q), self.scale, _ptr(self.truth32))
 
+    def _prepare_device(self, slot_ptr, slot_src, gnn, truth, is_edge, with_single, ordered, compact, scale):
+        """gtf_kl_prepare (include/gtf.h) on device tensors in the caller's order: slot_ptr int32
+        [N + 1], slot_src int32 [S], gnn float64 [N, 2] or [N, 4], truth int64 [N] or None, is_edge
+        uint8 [S] or None. Leaves the object the host constructor leaves, its host copies lazy."""
+        dev = slot_ptr.device
+        want = ((slot_ptr, torch.int32, "slot_ptr"), (slot_src, torch.int32, "slot_src"), (gnn, torch.float64, "gnn"),
+                (truth, torch.int64, "truth"), (is_edge, torch.uint8, "is_edge"))
+        for a, dt, name in want:
+            if a is not None and (a.dtype != dt or a.device != dev or not a.is_contiguous()):
+                raise ValueError("ParabolicKL: %s must be a contiguous %s tensor on %s" % (name, dt, dev))
+        N, S = int(slot_ptr.numel()) - 1, int(slot_src.numel())
+        if N < 0 or gnn.dim() != 2 or gnn.shape[0] != N or gnn.shape[1] not in (2, 4):
+            raise ValueError("ParabolicKL: slot_ptr holds N + 1 offsets and gnn is [N, 2] or [N, 4]")
+        if (truth is not None and truth.numel() != N) or (is_edge is not None and is_edge.numel() != S):
+            raise ValueError("ParabolicKL: one truth id per node, one is_edge byte per slot")
+        if scale is not None and not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError("quantise_xy: scale must be finite and > 0")
+        z = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=dev)  # noqa: E731
+        o_ptr, o_src, o_xy, o_pair = z(N + 1, torch.int32), z(S, torch.int32), z(2 * N, torch.float64), z(N + 1, torch.int64)
+        o_truth = z(N, torch.int64) if truth is not None else None
+        o_list = z(N, torch.int32) if not ordered else None
+        o_node = z(N, torch.int64) if ordered else None
+        o_slot = z(S, torch.int64) if ordered else None
+        o_q = z(2 * N, torch.int32) if compact else None
+        o_t32 = z(N, torch.int32) if compact and truth is not None else None
+        L = nat.lib()
+        nb = int(L.gtf_kl_prepare_workspace_bytes(N, S))
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        pin = nat.GtfKlPrepareIn(n_nodes=N, n_slots=S, slot_ptr=_ptr(slot_ptr), slot_src=_ptr(slot_src),
+                                 is_edge=_ptr(is_edge), gnn=_ptr(gnn), truth=_ptr(truth), gnn_stride=int(gnn.shape[1]),
+                                 with_single=int(bool(with_single)), layout=int(bool(ordered)), compact=int(bool(compact)),
+                                 scale=float(scale) if scale is not None else 0.0)
+        buf = nat.GtfKlPrepareBuf(_ptr(o_ptr), _ptr(o_src), _ptr(o_xy), _ptr(o_truth), _ptr(o_pair), _ptr(o_list),
+                                  _ptr(o_node), _ptr(o_slot), _ptr(o_q), _ptr(o_t32))
+        g, q, c = nat.GtfKlGraph(), nat.GtfKlQ32(), nat.GtfKlCounts()
+        s = torch.cuda.current_stream(dev)
+        rc = L.gtf_kl_prepare(ctypes.byref(pin), ctypes.byref(buf), ctypes.byref(g), ctypes.byref(q), ctypes.byref(c),
+                              _ptr(ws), nb, ctypes.c_void_p(s.cuda_stream))
+        if rc == -2 and c.error:
+            _raise_prepare_error(c)
+        nat.check(rc)
+        self.n_nodes, self.n_slots, self.n_pairs, self.n_listed = N, int(c.n_kept), int(c.n_pairs), int(c.n_listed)
+        self.tile = 0
+        self.device = dev
+        self.slot_ptr, self.slot_src, self.pair_ptr = o_ptr[:N + 1], o_src[:self.n_slots], o_pair[:N + 1]
+        self.gnn = o_xy[:2 * N].reshape(N, 2)
+        self.truth = o_truth[:N] if truth is not None else None
+        self._node_of_dev = o_node[:N] if ordered else None
+        self._slot_of_dev = o_slot[:self.n_slots] if ordered else None
+        if ordered:
+            self.lists = [torch.empty(0, dtype=torch.int32, device=dev) for _ in range(4)]   # (ranges, no lists)
+            self._ranges = [int(c.n_d1), int(c.count[0] - c.n_d1)] + [int(x) for x in c.n_deg] + [int(c.count[3])]
+            if os.environ.get("GTF_KL_DEG_RUNS", "1") == "0":   # (the round-3 ordered form, as the host constructor)
+                g.deg_runs = 0
+                for k in range(6):
+                    g.n_deg[k] = 0
+        else:
+            at = np.concatenate([[0], np.cumsum([int(x) for x in c.count])])
+            self.lists = [o_list[int(at[k]):int(at[k + 1])] for k in range(4)]
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.q = self.truth32 = self.scale = self._q = None
+        if compact:
+            self.q, self.scale = o_q[:2 * N].reshape(N, 2), float(c.scale)
+            self.truth32 = o_t32[:N] if truth is not None else None
+            self._q = q
+        self._g = g
+        self._keep = (o_ptr, o_src, o_xy, o_pair, o_truth, o_list, o_node, o_slot, o_q, o_t32)   # (the structs' targets)
+
+    @classmethod
+    def from_device(cls, slot_ptr, slot_src, gnn, truth=None, is_edge=None, with_single=False, ordered=False,
+                    compact=False, scale=None):
+        """The KL graph of arrays that are resident already (torch device tensors: slot_ptr int32
+        [N + 1], slot_src int32 [S], gnn float64 [N, 2] or [N, 4], truth int64 [N], is_edge uint8 [S]
+        marking the slots that are in-edges): gtf_kl_prepare on them, nothing is uploaded. What
+        ParabolicKL(*in_edge_csr, ..., prepare="host") builds from their downloads, array for array."""
+        k = cls.__new__(cls)
+        k._prepare_device(slot_ptr, slot_src, gnn, truth, is_edge, with_single, ordered, compact, scale)
+        return k
+
+    @classmethod
+    def from_device_graph(cls, d, truth=None, with_single=False, ordered=False, compact=False, scale=None):
+        """from_device on a natural-layout gtf.device.DeviceGraph's own slot_ptr, slot_src, is_edge and
+        gnn: one resident event (DeviceGraph.from_event) or the fused graph of a batch (from_events;
+        events share no edge, so no pair spans two). What from_graph(d.host_graph()[0]) computes.
+        truth: int64 [N], a host array (uploaded) or a device tensor."""
+        if getattr(d, "mem", None) != "torch" or d.layout != "natural":
+            raise ValueError("from_device_graph: a natural-layout DeviceGraph of torch tensors (mem='torch')")
+        N, S = int(d.n_nodes), int(d.n_slots)
+        if truth is not None and not torch.is_tensor(truth):
+            truth = torch.from_numpy(np.ascontiguousarray(truth, np.int64).reshape(-1)).to(d.device)
+        return cls.from_device(d.t["slot_ptr"].reshape(-1)[:N + 1], d.t["slot_src"].reshape(-1)[:S],
+                               d.t["gnn"].reshape(-1)[:4 * N].reshape(N, 4), truth, d.t["is_edge"].reshape(-1)[:S],
+                               with_single, ordered, compact, scale)
+
+    def _node_of_device(self):
+        """node_of as a device tensor (None: natural layout); a host-prepared object uploads it once"""
+        if "_node_of_dev" not in self.__dict__:
+            self._node_of_dev = (torch.from_numpy(np.ascontiguousarray(self.node_of, np.int64)).to(self.device)
+                                 if self.node_of is not None else None)
+        return self._node_of_dev
+
+    def rows_dev(self, out):
+        """The (node, i, j, emp_var) columns of the training rows as device tensors (gtf_kl_pair_rows):
+        pair_index() and the emp_var[node] gather of training_rows_csr, from the buffers ``out`` of a
+        run(); node in the caller's numbering. Stream-ordered."""
+        P = self.n_pairs
+        z = lambda dt: torch.empty(max(P, 1), dtype=dt, device=self.device)  # noqa: E731
+        node, i, j = z(torch.int64), z(torch.int64), z(torch.int64)
+        ev = out.get("emp_var")
+        er = z(ev.dtype) if ev is not None else None
+        s = torch.cuda.current_stream(self.device)
+        nat.check(nat.lib().gtf_kl_pair_rows(ctypes.byref(self._g), P, _ptr(self._node_of_device()), _ptr(ev),
+                                             nat.GTF_F64 if ev is None or ev.dtype == torch.float64 else nat.GTF_F32,
+                                             _ptr(node), _ptr(i), _ptr(j), _ptr(er), ctypes.c_void_p(s.cuda_stream)))
+        rows = {"node": node[:P], "i": i[:P], "j": j[:P]}
+        if er is not None:
+            rows["emp_var"] = er[:P]
+        return rows
+
     def _block_table(self, d, pair_ptr, margin=WIN_MARGIN):   # (rank < 16: 10 keys)
         """gtf_kl_graph.blk of the tiled layout: one record of 12 int32 per tile (first node,
         bucket-0 count, its one-edge count, the three- and four-edge counts that follow (0 and
@@ -259,12 +444,32 @@ class ParabolicKL:
         r.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         if gnn is None:
             r.gnn = cl(self.gnn)
+        elif torch.is_tensor(gnn):   # resident coordinates: gtf_kl_coords permutes and quantises them there
+            if (gnn.dtype != torch.float64 or gnn.device != self.gnn.device or not gnn.is_contiguous() or gnn.dim() != 2
+                    or gnn.shape[0] != self.n_nodes or gnn.shape[1] not in (2, 4)):
+                raise ValueError("replica: gnn as a tensor is a contiguous float64 [N, 2] or [N, 4] on %s" % self.device)
+            N = self.n_nodes
+            r.gnn = torch.empty(max(2 * N, 1), dtype=torch.float64, device=self.device)[:2 * N].reshape(N, 2)
+            if self.q is not None:
+                r.truth32 = cl(self.truth32)
+                r.q = torch.empty(max(2 * N, 1), dtype=torch.int32, device=self.device)[:2 * N].reshape(N, 2)
+            s = torch.cuda.current_stream(self.device)
+            nat.check(nat.lib().gtf_kl_coords(N, _ptr(gnn), int(gnn.shape[1]), _ptr(self._node_of_device()), _ptr(r.gnn),
+                                              _ptr(r.q) if self.q is not None else None,
+                                              self.scale if self.q is not None else 0.0, _ptr(r.err),
+                                              ctypes.c_void_p(s.cuda_stream)))
+            e = int(r.err.item())
+            if e:
+                r.err.zero_()
+                _raise_prepare_error(e)
+            if self.q is not None:
+                r._q = nat.GtfKlQ32(_ptr(r.q), r.scale, _ptr(r.truth32))
         else:
             gh = np.asarray(gnn, np.float64)[:, :2]
             if self.node_of is not None:
                 gh = gh[self.node_of]
             r.gnn = torch.from_numpy(np.ascontiguousarray(gh)).to(self.device)
-        if self.q is not None:   # the compact copy: re-quantised with the parent's scale
+        if self.q is not None and not torch.is_tensor(gnn):   # the compact copy: re-quantised with the parent's scale
             r.truth32 = cl(self.truth32)
             if gnn is None:
                 r.q = cl(self.q)
@@ -384,18 +589,25 @@ class ParabolicKL:
         return out
 
 
-def training_rows(g: TrackGraph, truth=None, dtype="f64", device="cuda"):
+def training_rows(g: TrackGraph, truth=None, dtype="f64", device="cuda", prepare="host"):
     """(node, i, j, kl_dist, emp_var, truth) rows of extract_metadata_trackml_parabolic_model.py
-    for one event graph, computed on the GPU (dtype "f64", "f32" or the compact "q32")."""
+    for one event graph, computed on the GPU (dtype "f64", "f32" or the compact "q32").
+    prepare "device": as training_rows_csr."""
     ptr, src = in_edge_csr(g)
-    return training_rows_csr(ptr, src, g.node["gnn"], truth, dtype, device)
+    return training_rows_csr(ptr, src, g.node["gnn"], truth, dtype, device, prepare)
 
 
-def training_rows_csr(slot_ptr, slot_src, gnn, truth=None, dtype="f64", device="cuda"):
-    k = ParabolicKL(slot_ptr, slot_src, gnn, truth, device, compact=dtype == "q32")
+def training_rows_csr(slot_ptr, slot_src, gnn, truth=None, dtype="f64", device="cuda", prepare="host"):
+    """prepare "device": the graph is built by gtf_kl_prepare and the node, i, j and emp_var columns by
+    gtf_kl_pair_rows (ParabolicKL.rows_dev); the same six host arrays."""
+    k = ParabolicKL(slot_ptr, slot_src, gnn, truth, device, compact=dtype == "q32", prepare=prepare)
     out = k.run(k.alloc(dtype, truth=truth is not None, emp="var"), dtype)
-    node, i, j = k.pair_index()
-    ev = out["emp_var"].cpu().numpy()[node]
+    if prepare == "device":
+        rows = k.rows_dev(out)
+        node, i, j, ev = (rows[c].cpu().numpy() for c in ("node", "i", "j", "emp_var"))
+    else:
+        node, i, j = k.pair_index()
+        ev = out["emp_var"].cpu().numpy()[node]
     tr = out["truth"].cpu().numpy() if "truth" in out else np.zeros(k.n_pairs, np.int8)
     flags = k.errors()
     if flags:

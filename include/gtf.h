@@ -44,6 +44,11 @@
  *   gtf_graph_concat, gtf_concat_columns, gtf_candidate_order_device_ev, gtf_event_split
  *                    -> no reference counterpart: a batch of events as one graph, in place of
  *                       running run_gnn_trackml_mod.sh once per event
+ *   gtf_kl_prepare, gtf_kl_coords, gtf_kl_pair_rows
+ *                    -> learn_KL_parabolic_model/src/generate_training_data/
+ *                       extract_metadata_trackml_parabolic_model.py:15-99 (the in-edges, their
+ *                       pairs and the (node, i, j, emp_var) columns of a row), as
+ *                       gtf/parabolic.py ParabolicKL restates them
  */
 #ifndef GTF_H
 #define GTF_H
@@ -1224,6 +1229,114 @@ typedef struct gtf_kl_out32 {
  * fields, blk -- in any of gtf_kl_graph's three layouts; g->gnn, g->gnn_stride and g->truth
  * are ignored. Pairs, moments and the error word are laid out as gtf_parabolic_kl's. */
 int gtf_parabolic_kl_q32(const gtf_kl_graph* g, const gtf_kl_q32* q, const gtf_kl_out32* out, gtf_stream_t stream);
+
+/* ---- The KL graph itself: gtf_kl_prepare -----------------------------------------------
+ * gtf/parabolic.py ParabolicKL.__init__ with tile = 0 (lines 154-278) on the device: from a
+ * slot CSR, the coordinates and the truth ids, DEVICE arrays in the caller's order, to every
+ * array a gtf_kl_graph / gtf_kl_q32 points to, equal element for element to what the
+ * constructor uploads. That constructor restates the input side of the reference's
+ * learn_KL_parabolic_model/src/generate_training_data (extract_metadata_trackml_parabolic_
+ * model.py:15-99: the in-edges of every node, their pairs i > j; utils.py:221-289 reads x, y);
+ * the orders and the fixed-point copy are this project's own. gtf_kl_prepare.hip. */
+typedef struct gtf_kl_prepare_in {
+    uint32_t struct_size;      /* sizeof(gtf_kl_prepare_in) as the caller compiled it */
+    uint32_t abi_version;      /* GTF_ABI_VERSION */
+    int32_t n_nodes, n_slots;  /* N, S: each at most 2^30 */
+    const int32_t* slot_ptr;   /* [N+1] starts at 0, does not decrease, ends at S (checked on the device) */
+    const int32_t* slot_src;   /* [S] sender of each slot; a kept slot's lies in [0, N) (checked on the device) */
+    const uint8_t* is_edge;    /* [S] or NULL = every slot is an edge. Non-zero: the slot is kept, in slot order
+                                  (parabolic.py:66-75 in_edge_csr); a dropped slot's slot_src is never read */
+    const double* gnn;         /* [N*gnn_stride] x, y(, z, r) in the caller's node order */
+    const int64_t* truth;      /* [N] truth_particle, or NULL */
+    int32_t gnn_stride;        /* 2 or 4 */
+    int32_t with_single;       /* one-edge nodes are listed (parabolic.py:174 lo = 1) */
+    int32_t layout;            /* 0 natural (bucket lists, :219, :261-265), 1 ordered with degree runs (:178-184, :199-213, :249-260) */
+    int32_t compact;           /* also the fixed-point coordinates and int32 truth ids (:267-278) */
+    double scale;              /* compact: 0 = derive (quantise_xy, :51-56), else used as it is */
+} gtf_kl_prepare_in;
+
+/* The caller's output arrays. Those a call does not need may be NULL. */
+typedef struct gtf_kl_prepare_buf {
+    int32_t* slot_ptr;         /* [N+1] */
+    int32_t* slot_src;         /* [S]; the first `kept slots` are written */
+    double* xy;                /* [N*2] */
+    int64_t* truth;            /* [N] with in.truth */
+    int64_t* pair_ptr;         /* [N+1] exclusive sum of d (d - 1) / 2 for d >= 2, else 0 (:215-217) */
+    int32_t* list;             /* [N] layout 0: the four bucket lists one after another, each ascending (:219);
+                                  the words after the n_listed-th are unspecified */
+    int64_t* node_of;          /* [N] layout 1: the stable argsort of the degree rank (:199, :212) */
+    int64_t* slot_of;          /* [S] layout 1: the in-edge CSR's slot of every new slot (:204) */
+    int32_t* q;                /* [N*2] compact: rint(x / scale) (:60-63), 8-byte aligned */
+    int32_t* truth32;          /* [N] compact with in.truth: the id where every id lies in [-2^31, 2^31), else its
+                                  rank among the sorted distinct signed ids (np.unique's inverse, :274-277) */
+} gtf_kl_prepare_buf;
+
+#define GTF_KL_ERR_SLOT_PTR  1u   /* slot_ptr does not start at 0, decreases or does not end at n_slots */
+#define GTF_KL_ERR_SOURCE    2u   /* a kept slot's source outside [0, N) */
+#define GTF_KL_ERR_NONFINITE 4u   /* compact: a NaN or inf coordinate (quantise_xy's ValueError, :49-50) */
+#define GTF_KL_ERR_FIT       8u   /* compact: some |q| >= 2^30 under the given scale (:61-62) */
+#define GTF_KL_ERR_SCALE     16u  /* compact: the derived scale is not finite and > 0 (:58-59) */
+#define GTF_KL_ERR_NODE_OF   32u  /* gtf_kl_coords: a node_of entry outside [0, N) */
+
+typedef struct gtf_kl_counts {
+    int32_t n_kept;            /* kept slots: the graph's n_slots */
+    int32_t n_listed;          /* nodes in the four buckets (:220) */
+    int64_t n_pairs;           /* pair_ptr[N] */
+    int32_t count[4];          /* gtf_kl_graph.count */
+    int32_t first[4];          /* gtf_kl_graph.first (layout 0: zero; list q starts at the sum of the counts before it) */
+    int32_t n_d1;
+    int32_t n_deg[6];
+    uint32_t error;            /* GTF_KL_ERR_* */
+    double scale;              /* compact: the scale used */
+    double max_abs;            /* compact: the largest finite |x|, |y| */
+} gtf_kl_counts;
+
+/* Scratch of gtf_kl_prepare: positive for zero sizes, non-decreasing in each argument (negative
+ * counts as 0). About 70 bytes per node and 12 per slot. */
+size_t gtf_kl_prepare_workspace_bytes(int32_t n_nodes, int32_t n_slots);
+
+/* ParabolicKL.__init__ line by line:
+ *   - with is_edge the kept slots in slot order and their slot_ptr (in_edge_csr);
+ *   - layout 1: rank = the first true key of [d == 1 if with_single] + [d == q for q in 2..8] +
+ *     [d > 8], 9 for unlisted nodes (:181-184); node_of = its stable argsort (:199), ONE stable
+ *     4-bit hipCUB radix pass; slot_ptr, slot_of, slot_src through the inverse order, x, y and
+ *     truth permuted (:200-211); count, first, n_d1, n_deg, deg_runs = 1 (:250-260);
+ *   - layout 0: the arrays in the caller's order and the bucket lists (:219), the same radix pass
+ *     on the bucket number; an empty list is NULL in *out;
+ *   - compact: one reduction for the largest |x|, |y|; scale = 2^(e - 30) with quantise_xy's
+ *     e += 1 step, e = 0 for all-zero input; q = rint(x / scale), ties to even. The scale stays
+ *     on the device for the quantising launch and comes back with the counts. The 64-bit sort of
+ *     the truth ids always runs and the writing kernel chooses by a device flag whether it
+ *     stores the ids or their ranks: ONE synchronisation, to fill *counts.
+ * The number of launches does not depend on N. No atomic but the error word's on a violation.
+ * Nothing is allocated. *out (gnn_stride 2, slot0 = pair0 = 0, no blk) and, with compact, *q32
+ * hold buf's pointers and the counts, ready for gtf_parabolic_kl / gtf_parabolic_kl_q32.
+ * Returns -2 with GTF_KL_ERR_* in counts->error and gtf_last_error() naming the rule (the
+ * arrays are then unspecified; nothing is written outside them); -3 for another ABI of *in; -2
+ * before any launch for a null argument or array that is needed, negative sizes, more than 2^30
+ * nodes or slots, another gnn_stride or layout, a negative or non-finite scale or a small
+ * workspace. N == 0 (then S == 0): slot_ptr[0] = pair_ptr[0] = 0 by two stream-ordered fills,
+ * no workspace needed. S == 0 is legal. */
+int gtf_kl_prepare(const gtf_kl_prepare_in* in, const gtf_kl_prepare_buf* buf, gtf_kl_graph* out, gtf_kl_q32* q32,
+                   gtf_kl_counts* counts, void* workspace, size_t workspace_bytes, gtf_stream_t stream);
+
+/* The coordinate step alone (parabolic.py:468-471 and :269, ParabolicKL.replica): gnn in the
+ * caller's node order, node_of [N] or NULL (identity); writes xy [N*2] and / or q [N*2] with the
+ * GIVEN scale, each NULL or written, by gtf_kl_prepare's own kernel. Stream-ordered, no
+ * synchronisation: GTF_KL_ERR_NONFINITE / _FIT / _NODE_OF are or-ed into the device word *err
+ * (required), which the caller clears and reads. */
+int gtf_kl_coords(int32_t n_nodes, const double* gnn, int32_t gnn_stride, const int64_t* node_of, double* xy, int32_t* q,
+                  double scale, uint32_t* err, gtf_stream_t stream);
+
+/* The columns of the training rows (parabolic.py:559-571 pair_index and the emp_var[node] gather
+ * of training_rows_csr, :609-610; extract_metadata_trackml_parabolic_model.py:61-99 writes one
+ * row per pair): for pair row p of node v (pair_ptr[v] <= p < pair_ptr[v + 1]; nodes without
+ * pairs are passed over), t = p - pair_ptr[v]: node[p] = node_of[v] (v with node_of NULL), i[p]
+ * the integer with i (i - 1) / 2 <= t < (i + 1) i / 2, j[p] = t - i (i - 1) / 2, emp_row[p] =
+ * emp_var[v] (dtype GTF_F64: double, GTF_F32: float; both NULL: no such column). g supplies
+ * n_nodes, pair_ptr and slot_ptr; n_pairs = pair_ptr[N]. Stream-ordered. */
+int gtf_kl_pair_rows(const gtf_kl_graph* g, int64_t n_pairs, const int64_t* node_of, const void* emp_var, int32_t dtype,
+                     int64_t* node, int64_t* i, int64_t* j, void* emp_row, gtf_stream_t stream);
 
 /* ---- event conversion: CSV rows -> packed CSR in the reference's orders -------------
  * Replaces helper.construct_graph + nx.DiGraph + the weakly-connected-component
