@@ -17,8 +17,14 @@
 // (the position -> neighbour table is staged in LDS), which is the reference's
 // value without a second pass.
 // The node's gradient mean/variance (np.mean / np.var over the set-order lists,
-// :440-441) is summed by lane 0 in numpy's pairwise order (sequential below 8
-// terms, 8 partial sums up to 128).
+// :440-441) is summed by lane 0 in numpy's pairwise order: sequential below 8 terms,
+// 8 partial sums up to 128, and beyond 128 numpy's recursion (halves, the left one
+// rounded down to a multiple of 8) on an explicit stack in the group's LDS stage,
+// which a node of more than 64 slots does not use otherwise.
+// The reference forms J S2 J^T with a dense diagonal S2, so a non-finite entry of J meets
+// the zeros of S2 and del_tau / del_theta are NaN there (never +-inf); zr_terms keeps that.
+// A key whose H is singular (x_B == 0, x_B == x_0 or x_0 == 0: np.linalg.inv raises,
+// :384) raises GTF_ERR_SINGULAR_H at its node when the caller passes a workspace.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -58,7 +64,8 @@ __device__ __forceinline__ ZrTerms zr_terms(const NodeGeo& n, const double* nb, 
     v = v + (j2 * (szn * szn)) * j2;
     v = v + (j3 * n.sr2) * j3;
     v = v + (j4 * (srn * srn)) * j4;
-    t.del_tau = v;
+    // (an infinite entry of J times an off-diagonal zero of S2: NaN in the reference's dense product)
+    t.del_tau = (isfinite(j1) && isfinite(j3)) ? v : NAN;
     t.theta = atan(1.0 / t.tau);
     t.theta2 = atan2(r2 - r1, z2 - z1);
     const double pre = -1.0 / (1.0 + t.tau * t.tau);
@@ -67,7 +74,7 @@ __device__ __forceinline__ ZrTerms zr_terms(const NodeGeo& n, const double* nb, 
     w = w + (k2 * (szn * szn)) * k2;
     w = w + (k3 * n.sr2) * k3;
     w = w + (k4 * (srn * srn)) * k4;
-    t.del_theta = w;
+    t.del_theta = (isfinite(k1) && isfinite(k3)) ? w : NAN;
     return t;
 }
 
@@ -88,34 +95,81 @@ __device__ __forceinline__ NodeGeo node_geo(const double* gnn, int v, const gtf_
     return n;
 }
 
-// numpy add.reduce over a contiguous float64 array (pairwise_sum): sequential below 8
-// terms, otherwise 8 interleaved partial sums combined pairwise, then the tail
+// numpy's pairwise_sum of at most 128 terms from a(lo): sequential below 8 terms, otherwise 8
+// interleaved partial sums combined pairwise, then the tail
 template <typename Get>
-__device__ __forceinline__ double np_sum(int n, Get a) {
+__device__ __forceinline__ double np_block(int lo, int n, Get a) {
     if (n < 8) {
         double s = 0.0;
-        for (int i = 0; i < n; i++) s += a(i);
+        for (int i = 0; i < n; i++) s += a(lo + i);
         return s;
     }
     double r[8];
-    for (int j = 0; j < 8; j++) r[j] = a(j);
+    for (int j = 0; j < 8; j++) r[j] = a(lo + j);
     int i = 8;
     for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; j++) r[j] += a(i + j);
+        for (int j = 0; j < 8; j++) r[j] += a(lo + i + j);
     double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) s += a(i);
+    for (; i < n; i++) s += a(lo + i);
     return s;
+}
+
+constexpr int NP_BLOCK = 128;    // numpy's PW_BLOCKSIZE
+constexpr int NP_FRAMES = 64;    // (lo, n) frames: two per level of the recursion and one, 31 levels at most
+
+// numpy add.reduce over a contiguous float64 array (pairwise_sum). Beyond 128 terms numpy
+// recurses: sum(a, n) = sum(a, n2) + sum(a + n2, n - n2) with n2 = n / 2 rounded down to a
+// multiple of 8. The recursion runs on an explicit stack: `frames` holds (lo, n) pairs still
+// to be summed (n < 0: add the two sums on top), `sums` the finished subtrees.
+// This is the recursion alone: the caller sums up to 128 terms with np_block(0, n, a), and calls this
+// from ONE place for its four sums: inlined at each of them it cost the whole kernel 17 % (seeded
+// 31,294-node event, no node beyond 128 keys: 35 -> 41 us per call); from one place the call takes
+// 38 us where the kernel without it took 37 (medians of 40 alternating calls).
+// Each term of a node beyond 64 slots is found by a search over the slots (O(d^2)), so one lane does
+// O(d^3) work per sum, as it already does for 65 to 128 keys.
+template <typename Get>
+__device__ __forceinline__ double np_sum_big(int n, Get a, int32_t* frames, double* sums) {
+    int sp = 0, ns = 0;
+    frames[0] = 0; frames[1] = n; sp = 1;
+    while (sp > 0) {
+        sp--;
+        const int lo = frames[2 * sp], len = frames[2 * sp + 1];
+        if (len < 0) { ns--; sums[ns - 1] = sums[ns - 1] + sums[ns]; continue; }
+        if (len <= NP_BLOCK) { sums[ns++] = np_block(lo, len, a); continue; }
+        int n2 = len / 2;
+        n2 -= n2 % 8;
+        frames[2 * sp] = 0; frames[2 * sp + 1] = -1; sp++;
+        frames[2 * sp] = lo + n2; frames[2 * sp + 1] = len - n2; sp++;
+        frames[2 * sp] = lo; frames[2 * sp + 1] = n2; sp++;   // the left half first
+    }
+    return sums[0];
 }
 
 template <int G>
 struct TseStage {
     int u[G];            // neighbour of each dict position
-    double gxy[G], gzr[G];
+    double gxy[G];       // (beyond 128 keys, where nothing is staged: np_sum_big's stack of finished sums)
+    union {
+        double gzr[G];
+        int32_t frames[2 * G];   // (beyond 128 keys: np_sum_big's (lo, n) frames)
+    };
 };
+
+static_assert(sizeof(TseStage<64>::frames) >= 2 * NP_FRAMES * sizeof(int32_t) && sizeof(TseStage<64>::gxy) >= 32 * sizeof(double),
+              "np_sum's stacks live in the 64-lane stage");
+
+// a reference exception at node v, reported as raise_node (gtf_pass.hip) does: the workspace's
+// error word and v's entry of the optional gtf_diag.node_err registered there
+__device__ __forceinline__ void raise_tse(uint32_t* err, int v, uint32_t f) {
+    atomicOr(err, f);
+    uint32_t* ne = reinterpret_cast<const gtf_diag*>(reinterpret_cast<const char*>(err) + GTF_DIAG_OFFSET)->node_err;
+    if (ne) atomicOr(ne + v, f);
+}
 
 template <int G>
 __device__ __forceinline__ void tse_node(const gtf_graph& g, gtf_states& tse, const gtf_tse_extra& x,
-                                         const gtf_params& p, const int32_t* list, int count, int bid, char* smem) {
+                                         const gtf_params& p, const int32_t* list, int count, int bid, char* smem,
+                                         uint32_t* err) {
     const int gi = (bid * BLOCK + (int)threadIdx.x) / G;
     const int gl = threadIdx.x & (G - 1);
     if (gi >= count) return;  // group-uniform
@@ -174,6 +228,10 @@ __device__ __forceinline__ void tse_node(const gtf_graph& g, gtf_states& tse, co
         const double xB = (xk - ng.x) * ng.ca + (yk - ng.y) * ng.sa;
         const double mB = -(xk - ng.x) * ng.sa + (yk - ng.y) * ng.ca;
         const double x0 = ng.x0;
+        // H is singular: np.linalg.inv raises (:384); the key's states below are then unspecified.
+        // A key that is the node itself (a self loop in the edge rows, which the builders keep as
+        // networkx does) is singular too and is not reported: see gtf.h.
+        if ((xB == 0.0 || xB == x0 || x0 == 0.0) && err && u != v) raise_tse(err, v, GTF_ERR_SINGULAR_H);
         const double r0 = 1.0 / (x0 * (x0 - xB)), r1 = 1.0 / (x0 * xB), r2 = 1.0 / (xB * (xB - x0));
         // columns of H^-1 (coefficients a = 2 alpha, b, c of the Lagrange basis)
         const double A0 = 2.0 * r0, B0 = -xB * r0;
@@ -213,6 +271,25 @@ __device__ __forceinline__ void tse_node(const gtf_graph& g, gtf_states& tse, co
     if (gl == 0) {
         if (x.xy_mean_var || x.zr_mean_var) {
             double gx[2], gz[2];
+            if (n > NP_BLOCK) {
+                // numpy's recursion, one instance of it: term sel = 2 w + (0: xy, 1: zr) of the loop below.
+                // Such a node is not staged, so its stage is free for the stacks.
+                double m[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma nounroll
+                for (int sel = 0; sel < 4; sel++) {
+                    auto term = [&](int i) -> double {
+                        int uu = -1;
+                        for (int j = lo; j < lo + d && uu < 0; j++)
+                            if (tse.rank[j] >= 0 && dict_pos(j) == n - 1 - i) uu = g.slot_src[j];
+                        const ZrTerms t = zr_terms(ng, g.gnn + 4 * (int64_t)uu, p);
+                        const double val = (sel & 1) ? t.tau : t.grad_xy;
+                        const double mean = m[sel & 1];
+                        return sel < 2 ? val : (val - mean) * (val - mean);
+                    };
+                    m[sel] = np_sum_big(n, term, stg->frames, stg->gxy) / (double)n;
+                }
+                gx[0] = m[0]; gz[0] = m[1]; gx[1] = m[2]; gz[1] = m[3];
+            } else
             for (int w = 0; w < 2; w++) {
                 // w = 0: the gradients; w = 1: squared deviations from their mean
                 auto getx = [&](int i) -> double {
@@ -237,8 +314,8 @@ __device__ __forceinline__ void tse_node(const gtf_graph& g, gtf_states& tse, co
                     }
                     return w == 0 ? val : (val - gz[0]) * (val - gz[0]);
                 };
-                gx[w] = np_sum(n, getx) / (double)n;   // n = 0 -> NaN, like np.mean([])
-                gz[w] = np_sum(n, getz) / (double)n;
+                gx[w] = np_block(0, n, getx) / (double)n;   // n = 0 -> NaN, like np.mean([])
+                gz[w] = np_block(0, n, getz) / (double)n;
             }
             if (x.xy_mean_var) { x.xy_mean_var[2 * (int64_t)v] = gx[0]; x.xy_mean_var[2 * (int64_t)v + 1] = gx[1]; }
             if (x.zr_mean_var) { x.zr_mean_var[2 * (int64_t)v] = gz[0]; x.zr_mean_var[2 * (int64_t)v + 1] = gz[1]; }
@@ -262,26 +339,26 @@ constexpr size_t tse_smem() {
 
 // one launch over the slot-count buckets, long-running ones first
 __global__ void __launch_bounds__(BLOCK) k_tse(gtf_graph g, gtf_states tse, gtf_tse_extra x, gtf_params p,
-                                               TseBuckets bk) {
+                                               TseBuckets bk, uint32_t* err) {
     __shared__ __attribute__((aligned(16))) char smem[tse_smem() > (size_t)(BLOCK / 16) * sizeof(TseStage<16>)
                                                           ? tse_smem()
                                                           : (size_t)(BLOCK / 16) * sizeof(TseStage<16>)];
     int b = blockIdx.x;
-    if (b < bk.blocks[0]) { tse_node<64>(g, tse, x, p, bk.list[0], bk.count[0], b, smem); return; }  // > 64 slots
+    if (b < bk.blocks[0]) { tse_node<64>(g, tse, x, p, bk.list[0], bk.count[0], b, smem, err); return; }  // > 64 slots
     b -= bk.blocks[0];
-    if (b < bk.blocks[1]) { tse_node<64>(g, tse, x, p, bk.list[1], bk.count[1], b, smem); return; }
+    if (b < bk.blocks[1]) { tse_node<64>(g, tse, x, p, bk.list[1], bk.count[1], b, smem, err); return; }
     b -= bk.blocks[1];
-    if (b < bk.blocks[2]) { tse_node<32>(g, tse, x, p, bk.list[2], bk.count[2], b, smem); return; }
+    if (b < bk.blocks[2]) { tse_node<32>(g, tse, x, p, bk.list[2], bk.count[2], b, smem, err); return; }
     b -= bk.blocks[2];
-    if (b < bk.blocks[3]) { tse_node<16>(g, tse, x, p, bk.list[3], bk.count[3], b, smem); return; }
+    if (b < bk.blocks[3]) { tse_node<16>(g, tse, x, p, bk.list[3], bk.count[3], b, smem, err); return; }
     b -= bk.blocks[3];
-    tse_node<8>(g, tse, x, p, bk.list[4], bk.count[4], b, smem);
+    tse_node<8>(g, tse, x, p, bk.list[4], bk.count[4], b, smem, err);
 }
 
 }  // namespace
 
-extern "C" int gtf_track_state_estimates(const gtf_graph* g, gtf_states* tse, const gtf_tse_extra* x,
-                                         const gtf_params* p, gtf_stream_t stream) {
+extern "C" int gtf_track_state_estimates_ws(const gtf_graph* g, gtf_states* tse, const gtf_tse_extra* x,
+                                            const gtf_params* p, void* workspace, gtf_stream_t stream) {
     if (int rc = gtf::check_abi(g, "gtf_track_state_estimates")) return rc;
     if (!tse || !x || !p) { gtf::set_error("gtf_track_state_estimates: null argument"); return -2; }
     if (g->n_nodes < 0 || g->n_slots < 0) { gtf::set_error("gtf_track_state_estimates: negative sizes"); return -2; }
@@ -310,8 +387,14 @@ extern "C" int gtf_track_state_estimates(const gtf_graph* g, gtf_states* tse, co
         bk.blocks[i] = (bk.count[i] + BLOCK / gs[i] - 1) / (BLOCK / gs[i]);
         total += bk.blocks[i];
     }
-    hipLaunchKernelGGL(k_tse, dim3(total), dim3(BLOCK), 0, (hipStream_t)stream, *g, *tse, *x, *p, bk);
+    hipLaunchKernelGGL(k_tse, dim3(total), dim3(BLOCK), 0, (hipStream_t)stream, *g, *tse, *x, *p, bk,
+                       (uint32_t*)workspace);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { gtf::set_error(hipGetErrorString(e)); return -1; }
     return 0;
+}
+
+extern "C" int gtf_track_state_estimates(const gtf_graph* g, gtf_states* tse, const gtf_tse_extra* x,
+                                         const gtf_params* p, gtf_stream_t stream) {
+    return gtf_track_state_estimates_ws(g, tse, x, p, nullptr, stream);
 }

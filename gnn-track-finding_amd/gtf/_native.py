@@ -498,7 +498,7 @@ ERR_FLAGS = {
     16: "ZeroDivisionError: empty state dict (helper.py:90)",
     32: "ValueError: NaN KL distance (clustering.py:117)",
     64: "KeyError: node has no state dict (remove_state_metadata.py:39)",
-    128: "LinAlgError: singular parabola matrix H (learn_KL_parabolic_model utils.py:277)",
+    128: "LinAlgError: singular parabola matrix H (helper.py:384; learn_KL_parabolic_model utils.py:277)",
     256: "pair_ptr disagrees with the updated_track_states dicts (caller error)",
     512: "KeyError: neighbour not in the subgraph (calculate_distance_between_updated_track_states.py:182-183)",
     1024: "a node holds more than 2048 updated track states (not processed)",
@@ -507,7 +507,7 @@ ERR_FLAGS = {
 # exported symbols (must match include/gtf.h; tests check the .so exports all of them)
 SYMBOLS = ["gtf_workspace_bytes", "gtf_workspace_init", "gtf_uts_materialize", "gtf_clear_errors", "gtf_read_errors", "gtf_extrapolate", "gtf_update",
            "gtf_message_passing", "gtf_node_ops",
-           "gtf_cluster", "gtf_pass", "gtf_pass_ev", "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_tag_workspace_bytes", "gtf_tag_propagate", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_pass_shard",
+           "gtf_cluster", "gtf_pass", "gtf_pass_ev", "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_tag_workspace_bytes", "gtf_tag_propagate", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_track_state_estimates_ws", "gtf_pass_shard",
            "gtf_shard_chunk_bytes", "gtf_shard_pack", "gtf_shard_unpack", "gtf_halo_pack", "gtf_halo_unpack",
            "gtf_extract_workspace_bytes",
            "gtf_extract_candidates", "gtf_build_event_csr", "gtf_candidate_order",
@@ -662,6 +662,7 @@ def lib(lean: bool = False):
     L.gtf_halo_pack.argtypes = [N, E, HA, P, P]
     L.gtf_halo_unpack.argtypes = [N, E, HA, P, P]
     L.gtf_track_state_estimates.argtypes = [G, S, ctypes.POINTER(GtfTseExtra), PR, P]
+    L.gtf_track_state_estimates_ws.argtypes = [G, S, ctypes.POINTER(GtfTseExtra), PR, P, P]
     L.gtf_parabolic_kl.argtypes = [ctypes.POINTER(GtfKlGraph), I32, ctypes.POINTER(GtfKlOut), P]
     L.gtf_parabolic_kl_q32.argtypes = [ctypes.POINTER(GtfKlGraph), ctypes.POINTER(GtfKlQ32),
                                        ctypes.POINTER(GtfKlOut32), P]
@@ -737,7 +738,7 @@ def lib(lean: bool = False):
     L.gtf_version.restype = ctypes.c_char_p
     for fn in ("gtf_workspace_init", "gtf_uts_materialize", "gtf_clear_errors", "gtf_read_errors", "gtf_extrapolate", "gtf_update", "gtf_cluster", "gtf_pass",
                "gtf_pass_ev", "gtf_message_passing", "gtf_node_ops",
-               "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_pass_shard", "gtf_shard_pack",
+               "gtf_tag_prepare", "gtf_tag_sweep", "gtf_tag_sweep_shard", "gtf_parabolic_kl", "gtf_parabolic_kl_q32", "gtf_track_state_estimates", "gtf_track_state_estimates_ws", "gtf_pass_shard", "gtf_shard_pack",
                "gtf_shard_unpack", "gtf_halo_pack", "gtf_halo_unpack", "gtf_extract_candidates", "gtf_build_event_csr",
                "gtf_candidate_order", "gtf_updated_state_pair_counts", "gtf_updated_state_distances",
                "gtf_set_diagnostics", "gtf_build_event_csr_device", "gtf_device_init", "gtf_malloc", "gtf_free",

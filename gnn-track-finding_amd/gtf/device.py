@@ -617,7 +617,9 @@ class DeviceGraph:
         returns the per-node attributes (xy/zr_edge_gradient_mean_var,
         angle_of_rotation, translation) as device tensors -- in host node order, or with
         host_order=False in the device layout's order (no gathers: what a caller that keeps
-        the event on the device consumes)."""
+        the event on the device consumes). A key whose parabola matrix is singular
+        (np.linalg.inv raises, helper.py:384) sets GTF_ERR_SINGULAR_H in errors() and in the
+        node's entry of the node_err diagnostics; raise_errors() raises for it."""
         self._natural_only("track_state_estimates")
         if self.torch is None:
             return self._track_state_estimates_hip(p, host_order)
@@ -632,8 +634,9 @@ class DeviceGraph:
         ex = nat.GtfTseExtra(self.ptr("tse_theta"), self.ptr("tse_var_ms"), vp(x["xy_mean_var"]),
                              vp(x["zr_mean_var"]), vp(x["angle_of_rotation"]), vp(x["translation"]))
         cp = self.cparams(p)
-        nat.check(self.lib.gtf_track_state_estimates(ctypes.byref(self.cg_sched), ctypes.byref(self.ctse),
-                                                     ctypes.byref(ex), ctypes.byref(cp), self.stream))
+        nat.check(self.lib.gtf_track_state_estimates_ws(ctypes.byref(self.cg_sched), ctypes.byref(self.ctse),
+                                                        ctypes.byref(ex), ctypes.byref(cp), self.ptr("ws"),
+                                                        self.stream))
         if self.order is not None and host_order:   # per-node outputs in host node order
             inv = self._inv_order()
             x = {k: v[inv] for k, v in x.items()}
@@ -650,8 +653,9 @@ class DeviceGraph:
         ex = nat.GtfTseExtra(self.ptr("tse_theta"), self.ptr("tse_var_ms"), vp(x["xy_mean_var"]),
                              vp(x["zr_mean_var"]), vp(x["angle_of_rotation"]), vp(x["translation"]))
         cp = self.cparams(p)
-        nat.check(self.lib.gtf_track_state_estimates(ctypes.byref(self.cg_sched), ctypes.byref(self.ctse),
-                                                     ctypes.byref(ex), ctypes.byref(cp), self.stream))
+        nat.check(self.lib.gtf_track_state_estimates_ws(ctypes.byref(self.cg_sched), ctypes.byref(self.ctse),
+                                                        ctypes.byref(ex), ctypes.byref(cp), self.ptr("ws"),
+                                                        self.stream))
         out = {k: v.numpy().reshape(shapes[k]) for k, v in x.items()}
         if self.order is not None and host_order:
             inv = np.empty(self.order.size, np.int64)

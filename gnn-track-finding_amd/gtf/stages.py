@@ -80,7 +80,11 @@ def compute_track_state_estimates(GraphList, sigma0xy, sigma0rz, sigma0rz2, endc
     p = Params(sigma0xy=sigma0xy, sigma0rz=sigma0rz, sigma0rz2=sigma0rz2, endcap_boundary=endcap_boundary)
     from .devmem import default_mem
     d = DeviceGraph(g, mem=default_mem())
+    d.clear_errors()
     x = {k: v if isinstance(v, np.ndarray) else v.cpu().numpy() for k, v in d.track_state_estimates(p).items()}
+    if d.errors() & 128:   # GTF_ERR_SINGULAR_H: np.linalg.inv(H) raises in the reference (helper.py:384)
+        from ._native import ERR_FLAGS
+        raise np.linalg.LinAlgError(ERR_FLAGS[128])
     d.download(g)
     S = g.slot
     vi = 0

@@ -249,7 +249,7 @@ enum {
     GTF_ERR_EMPTY_DICT_MW = 16,    /* ZeroDivisionError helper.py:90; nothing is written for the node */
     GTF_ERR_NAN_KL = 32,           /* ValueError clustering.py:117 (list.index of NaN); the merged state formed so far is stored and the keys still in the list are deactivated */
     GTF_ERR_NO_STATE_DICT = 64,    /* KeyError remove_state_metadata.py:39 */
-    GTF_ERR_SINGULAR_H = 128,      /* LinAlgError learn_KL_parabolic_model/.../utils.py:277 (x_B = 0 or x_B = x_0) */
+    GTF_ERR_SINGULAR_H = 128,      /* LinAlgError learn_KL_parabolic_model/.../utils.py:277 (x_B = 0 or x_B = x_0) and helper.py:384 (those and x_0 = 0; gtf_track_state_estimates_ws) */
     GTF_ERR_PAIR_COUNT = 256,      /* pair_ptr disagrees with the state dicts (caller error, a15) */
     GTF_ERR_NEIGHBOUR_MISSING = 512, /* KeyError calculate_distance_between_updated_track_states.py:182-183 */
     GTF_ERR_TOO_MANY_STATES = 1024 /* a15: a node with more than 2048 updated states (not processed) */
@@ -518,7 +518,15 @@ int gtf_tag_propagate_shard(gtf_comm* comm, const gtf_graph* g, const gtf_shard*
  * Pairs of node v are written at [pair_ptr[v] + t], t = i (i - 1) / 2 + j (the reference's
  * loop order). gtf_updated_state_pair_counts writes each node's pair count (0 or d(d-1)/2)
  * for the caller's exclusive scan into pair_ptr [N+1]; a node whose pair_ptr range has
- * another size is skipped with GTF_ERR_PAIR_COUNT. Uses g->sched when present. */
+ * another size is skipped with GTF_ERR_PAIR_COUNT. Uses g->sched when present; with
+ * g->sched == NULL every node runs on the one-wavefront path, to the same bits.
+ * A pair whose C_i + C_j is exactly singular (the reference's np.linalg.inv raises
+ * LinAlgError, :37) raises nothing here: its chi2 is left non-finite (NaN or +-inf), its
+ * other columns are what they are for any pair, and no other pair is affected. Where r of
+ * a neighbour equals the node's r the columns are non-finite in the reference's kind.
+ * A node that raises an error bit (a pair_ptr range of another size; a present key with
+ * slot_src < 0, the KeyError of :182-183; more than 2048 keys) has none of its pairs
+ * written; every other node of the call is. */
 typedef struct gtf_pair_out {
     double* chi2;         /* [P] */
     double* avg_tau;      /* [P] or NULL */
@@ -555,6 +563,30 @@ typedef struct gtf_tse_extra {
 
 int gtf_track_state_estimates(const gtf_graph* g, gtf_states* tse, const gtf_tse_extra* extra,
                               const gtf_params* p, gtf_stream_t stream);
+/* The same with the reference's exception reported. np.linalg.inv(H) raises LinAlgError
+ * (helper.py:384) for a key whose parabola matrix is singular: x_B == 0 (the neighbour has the
+ * node's own x, y), x_B == x_0 (the neighbour lies at the origin) or x_0 == 0 (the node lies
+ * at the origin), compared on the fp64 values. With workspace != NULL (an initialised
+ * gtf_workspace_bytes() block) the key's node then raises GTF_ERR_SINGULAR_H as the pass
+ * kernels raise: into the workspace's error word and, where gtf_diag.node_err is registered,
+ * into the node's entry. What the singular key's own outputs hold (sv, cov, tau, xyzr, theta,
+ * var_ms) is unspecified; every other key of the node, the node's per-node outputs and every
+ * other node are what they are without the singular key raising.
+ * One singular key is NOT reported: a key that is the node itself (slot_src == the node), which
+ * a self loop among the edge rows leaves in the dict (the builders keep such rows, as networkx
+ * does). The reference raises there as well (x_B == 0); the pipelines have always converted
+ * such events and gone on, the self key's own states being non-finite and every other state
+ * exact, and that stays so. A caller that wants the reference's stop tests slot_src itself.
+ * workspace == NULL is
+ * gtf_track_state_estimates: nothing is reported. No output array changes with the workspace,
+ * and a call in which no key is singular writes nothing to it.
+ * Non-finite results have the reference's kind: where r or x of node and neighbour coincide
+ * the reference's dense J S2 J^T multiplies infinities by zeros, so del_tau^2 and
+ * variance_theta are NaN there, not +inf.
+ * The node sums (np.mean / np.var of the gradients) are numpy's pairwise sums at every key
+ * count, its recursion beyond 128 terms included. */
+int gtf_track_state_estimates_ws(const gtf_graph* g, gtf_states* tse, const gtf_tse_extra* extra,
+                                 const gtf_params* p, void* workspace, gtf_stream_t stream);
 
 /* ---- Track-candidate extraction ---------------------------
  * src/extract/extract_track_candidates.py main (:349-467) on the pass's output: CCA

@@ -696,7 +696,7 @@ def parabolic_training_rows(g: TrackGraph, truth=None):
             np.asarray(a[3], np.float64), np.asarray(a[4], np.float64), np.asarray(a[5], np.int8))
 
 
-def compute_track_state_estimates(g: TrackGraph, p):
+def compute_track_state_estimates(g: TrackGraph, p, singular=None):
     """helper.compute_track_state_estimates (helper.py:238-452) on the packed layout.
 
     The dict order of each node's track_state_estimates is the INPUT ``tse_rank``
@@ -706,7 +706,13 @@ def compute_track_state_estimates(g: TrackGraph, p):
     returns the node arrays (xy_mean_var, zr_mean_var, angle_of_rotation,
     translation). The per-neighbour lists gradients_zr / del_tau / theta are
     filled in set order but read with the dict-order index (:384, :419-431) --
-    reproduced as is."""
+    reproduced as is.
+
+    np.linalg.inv raises LinAlgError for a singular H (:384: x_B == 0, x_B == x_0 or
+    x_0 == 0), and so does this function, naming that line. With ``singular`` a list, the
+    (node, slot) of every such key is appended instead, the key's outputs stay as they
+    were and the other keys and nodes go on: what gtf_track_state_estimates_ws leaves
+    beside GTF_ERR_SINGULAR_H."""
     S = np.array([[4.0**2, 0, 0], [0, p.sigma0xy**2, 0], [0, 0, p.sigma0xy**2]])
     gnn = g.node["gnn"]
     N = g.n_nodes
@@ -751,7 +757,13 @@ def compute_track_state_estimates(g: TrackGraph, p):
             x_B = (xk - xA) * ca + (yk - yA) * sa
             m_B = -(xk - xA) * sa + (yk - yA) * ca
             H = np.array([[0.5 * x_0**2, x_0, 1], [0.0, 0.0, 1], [0.5 * x_B**2, x_B, 1]])
-            H_inv = np.linalg.inv(H)
+            try:
+                H_inv = np.linalg.inv(H)
+            except np.linalg.LinAlgError as exc:
+                if singular is None:
+                    raise np.linalg.LinAlgError("LinAlgError: %s (helper.py:384)" % exc) from exc
+                singular.append((v, int(k)))
+                continue
             sv = H_inv.dot([0.0, 0.0, m_B])
             a, b = sv[0], sv[1]
             dr, dz = rA - rk, zA - zk

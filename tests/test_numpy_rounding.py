@@ -170,3 +170,58 @@ def test_shared_reciprocal_division_is_exact(rng):
             ref = np.float64(x) / np.float64(d)
             got = qdiv(x, d, float(np.float64(1.0) / np.float64(d)))
             assert got == ref or (np.isnan(got) and np.isnan(ref)), (x, d)
+
+
+def np_block(a, lo, n):
+    """csrc/gtf_tse.hip np_block: numpy's pairwise_sum of at most 128 terms"""
+    if n < 8:
+        s = 0.0
+        for i in range(n):
+            s += a[lo + i]
+        return s
+    r = [a[lo + j] for j in range(8)]
+    i = 8
+    while i < n - (n % 8):
+        for j in range(8):
+            r[j] += a[lo + i + j]
+        i += 8
+    s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    while i < n:
+        s += a[lo + i]
+        i += 1
+    return s
+
+
+def np_sum(a):
+    """csrc/gtf_tse.hip np_sum: beyond 128 terms numpy's recursion, on the kernel's explicit stack
+    (frames of (lo, n) still to be summed, n < 0: add the two sums on top)"""
+    n = len(a)
+    if n <= 128:
+        return np_block(a, 0, n)
+    frames, sums = [(0, n)], []
+    depth = 0
+    while frames:
+        lo, ln = frames.pop()
+        if ln < 0:
+            top = sums.pop()
+            sums[-1] = sums[-1] + top
+        elif ln <= 128:
+            sums.append(np_block(a, lo, ln))
+        else:
+            n2 = ln // 2
+            n2 -= n2 % 8
+            frames += [(0, -1), (lo + n2, ln - n2), (lo, n2)]
+        depth = max(depth, len(frames))
+    assert depth <= 64 and len(sums) == 1   # NP_FRAMES of the kernel
+    return sums[0]
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 130, 136, 200, 257, 1000, 2049])
+def test_pairwise_sum_of_the_gradient_moments(rng, n):
+    """np.mean / np.var of helper.py:440-441 sum with np.add.reduce; the kernel's order is numpy's at
+    every length, the recursion above 128 terms included"""
+    for _ in range(2000 if n <= 257 else 200):
+        a = rng.normal(size=n) * 10.0 ** rng.uniform(-3, 3, n)
+        assert np_sum(list(a)) == np.add.reduce(a), n
+        m = np_sum(list(a)) / n if n else 0.0
+        assert n == 0 or (m == np.mean(list(a)) and np_sum(list((a - m) * (a - m))) / n == np.var(list(a)))
