@@ -23,6 +23,12 @@
 // sv[2] = 0 and cov[2][2] = s1 for every state, so the KL terms of component 2
 // vanish and a state is 7 numbers in LDS: sv0, sv1, c00, c11, i00, i01, i11.
 //
+// Singular H. GTF_ERR_SINGULAR_H is raised by the geometric rule xB == 0, xB == x0 or x0 == 0 on the
+// kernel's own rotation (x / h, -y / h): wherever the reference raises LinAlgError, and additionally
+// at exact geometric singularity where the reference, rotating by cos / sin(2 pi - atan2), meets a
+// pivot of a few ulp and returns unbounded values instead (include/gtf.h at gtf_parabolic_kl;
+// recorded image by image in tests/golden/kl_cases.npz).
+//
 // Two coordinate sources share the kernels (the paths below): gtf_parabolic_kl reads fp64
 // rows and int64 truth ids; gtf_parabolic_kl_q32 reads 32-bit fixed-point coordinates and
 // int32 ids, half the bytes per node, and computes in fp32 throughout.

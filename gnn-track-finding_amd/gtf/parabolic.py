@@ -34,7 +34,11 @@ WIN_MARGIN = 128   # window nodes either side of a tile (99 % of the vol-7 neigh
 
 
 def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+    if t is None:
+        return ctypes.c_void_p(0)
+    if t.numel() == 0 and t._base is not None:   # an empty view of a one-element buffer (an empty event's
+        t = t._base                               # arrays): its own data_ptr() is null, the buffer's is not
+    return ctypes.c_void_p(t.data_ptr())
 
 
 def quantise_xy(gnn, scale=None):
@@ -221,7 +225,14 @@ class ParabolicKL:
         self.degree = d
         self.pair_ptr_host = pair_ptr
         dev = torch.device(device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+
+        def t(a):
+            # an empty array (no node, no slot) as an empty view of a one-element buffer: _ptr passes
+            # the buffer's address, since the C-ABI takes a null pointer for a missing array
+            a = np.ascontiguousarray(a)
+            if a.size:
+                return torch.from_numpy(a).to(dev)
+            return torch.empty(1, dtype=torch.from_numpy(a).dtype, device=dev)[:0].reshape(a.shape)
         self.slot_ptr = t(slot_ptr)
         self.slot_src = t(np.asarray(slot_src, np.int32))
         # the kernel reads GNN_Measurement x and y only: a compact [N, 2] copy (gnn_stride 2)
@@ -267,14 +278,15 @@ class ParabolicKL:
     def _set_compact(self, gnn, truth, scale=None):
         """upload the fixed-point coordinates (device node order) and int32 truth ids"""
         q, self.scale = quantise_xy(np.asarray(gnn, np.float64)[:, :2], scale)
-        self.q = torch.from_numpy(q).to(self.device)
+        self.q = torch.from_numpy(q).to(self.device) if q.size else torch.empty(2, dtype=torch.int32, device=self.device)[:0].reshape(0, 2)
         if truth is not None and self.truth32 is None:
             # the kernel only compares ids: those that fit int32 go as they are, others (TrackML
             # particle ids are 60-bit numbers) as dense labels, equal exactly where the ids are
             t64 = np.asarray(truth, np.int64)
             if t64.size and (t64.min() < -2**31 or t64.max() >= 2**31):
                 t64 = np.unique(t64, return_inverse=True)[1].reshape(-1)
-            self.truth32 = torch.from_numpy(np.ascontiguousarray(t64.astype(np.int32))).to(self.device)
+            self.truth32 = (torch.from_numpy(np.ascontiguousarray(t64.astype(np.int32))).to(self.device) if t64.size
+                            else torch.empty(1, dtype=torch.int32, device=self.device)[:0])
         self._q = nat.GtfKlQ32(_ptr(self.q), self.scale, _ptr(self.truth32))
 
     def _prepare_device(self, slot_ptr, slot_src, gnn, truth, is_edge, with_single, ordered, compact, scale):

@@ -1229,7 +1229,19 @@ typedef struct gtf_kl_out {
 
 /* dtype: GTF_F64 computes states and distances in fp64 (the reference's precision);
  * GTF_F32 rotates/translates in fp64 and forms states and distances in fp32 (the
- * config-5 tolerance sweep). sv/cov outputs are fp64 in both modes. */
+ * config-5 tolerance sweep). sv/cov outputs are fp64 in both modes.
+ *
+ * GTF_ERR_SINGULAR_H. The flag is geometric: it is raised for an in-edge of a listed node whose
+ * x_B == 0, x_B == x_0 or x_0 == 0, compared on the fp64 values of the kernel's own rotation
+ * (cos, sin = x / h, -y / h; gtf_parabolic_kl_q32: on its fp32 values from the fixed-point
+ * coordinates). That is wherever the reference raises LinAlgError (utils.py:285 on H, or the
+ * script's own np.linalg.inv of the garbage covariance, :78), and additionally at exact geometric
+ * singularity where the reference does not raise: rotating by cos / sin(2 pi - atan2) leaves it a
+ * pivot of a few ulp there and it returns unbounded values (covariance entries of 1e14 to 1e28),
+ * e.g. node (10, 0) with neighbour (10, 5), or any node with a neighbour at the origin. The
+ * record of both behaviours, image by image, is tests/golden/kl_cases.npz (tests/kl_cases.py).
+ * The raising edge's state and its pairs are not finite; every other output of the call is
+ * written as usual. */
 int gtf_parabolic_kl(const gtf_kl_graph* g, int32_t dtype, const gtf_kl_out* out, gtf_stream_t stream);
 
 /* Compact input mode (gtf.parabolic.ParabolicKL(compact=True)): the same states, distances,

@@ -8,7 +8,10 @@
   its beyond-LDS recompute path).
 * States: edge_state_vector / edge_covariance per in-edge vs the oracle.
 * fp32: the config-5 sweep's fp32 mode stays within its stated envelope.
-* Singular H raises LinAlgError like np.linalg.inv.
+* Singular H: the geometric rule raises GTF_ERR_SINGULAR_H (see test_gpu_singular_raises).
+
+The exact-arithmetic distance that _check_rows_vs_oracle falls back on is kl_cases.exact_kl (50-digit
+decimal), shared with the directed cases of test_gpu_kl_cases.py.
 """
 import os
 import numpy as np
@@ -17,6 +20,7 @@ import pytest
 import gtf_oracle as O
 from gtf import synth
 from gtf.graph import TrackGraph
+from kl_cases import exact_kl as _true_kl
 from test_kat_parabolic import kat2_event, kat2_match, kat_event, kat_rows, sorted_rows
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -52,34 +56,6 @@ def test_gpu_rows_match_kat2():
     assert kl.size == 1055
     missing = kat2_match(kl, ev, tr.astype(np.float64))
     assert len(missing) == 1 and g.node["node_id"][node[missing[0]]] == 1635, missing
-
-
-def _true_kl(node, a, b):
-    """KLDistance of the exact-arithmetic parabolic states of neighbours a, b of node
-    (50-digit decimal; the rotation with exact cos/sin of atan2)."""
-    from decimal import Decimal as D, getcontext
-    getcontext().prec = 50
-    x, y = D(float(node[0])), D(float(node[1]))
-    h = (x * x + y * y).sqrt()
-    ca, sa = x / h, -y / h
-    xt, yt = x * ca - y * sa, x * sa + y * ca
-    x0 = -xt
-    s0, s1 = D(16), D(0.1) * D(0.1)
-
-    def state(nb):
-        xb, yb = D(float(nb[0])), D(float(nb[1]))
-        xB, mB = xb * ca - yb * sa - xt, xb * sa + yb * ca - yt
-        r0, r1, r2 = 1 / (x0 * (x0 - xB)), 1 / (x0 * xB), 1 / (xB * (xB - x0))
-        a0, b0, a1, b1, a2, b2 = r0, -xB * r0, r1, -(x0 + xB) * r1, r2, -x0 * r2
-        return (mB * a2, mB * b2, s0 * a0 * a0 + s1 * a1 * a1 + s1 * a2 * a2,
-                s0 * b0 * b0 + s1 * b1 * b1 + s1 * b2 * b2,
-                x0 ** 4 / s0 + xB ** 4 / s1, x0 ** 3 / s0 + xB ** 3 / s1, x0 ** 2 / s0 + xB ** 2 / s1)
-
-    p, q = state(a), state(b)
-    tr = (p[2] - q[2]) * (q[4] - p[4]) + (p[3] - q[3]) * (q[6] - p[6])
-    d0, d1 = p[0] - q[0], p[1] - q[1]
-    S00, S01, S11 = p[4] + q[4], p[5] + q[5], p[6] + q[6]
-    return float(tr + d0 * (d0 * S00 + d1 * S01) + d1 * (d0 * S01 + d1 * S11))
 
 
 def _check_rows_vs_oracle(g, truth, tol):
@@ -154,6 +130,12 @@ def test_gpu_fp32_envelope():
 
 
 def test_gpu_singular_raises():
+    """The flag is raised wherever the reference raises, and additionally at exact geometric singularity
+    (x_B == 0, x_B == x_0 or x_0 == 0 in the kernel's rotation), where the reference returns unbounded
+    values. This input, node (10, 0) with neighbour (10, 5), is of the second kind: the reference's
+    rotation by cos / sin(2 pi - atan2) leaves x_B a few ulp from 0, np.linalg.inv does not raise and the
+    state it returns has sv ~ 2.8e14 and cov[0][0] ~ 6e25 (recorded as sing_perp_axis_0 in
+    tests/golden/kl_cases.npz; its image (-10, 0) / (-10, 5) raises in the reference too)."""
     from gtf import parabolic
     # node 1 at (10, 0); neighbour 0 at the same x after rotation (x_B = 0)
     gnn = np.array([[10.0, 5.0, 0, 11.18], [10.0, 0.0, 0, 10.0], [20.0, 1.0, 0, 20.0]])
@@ -162,7 +144,7 @@ def test_gpu_singular_raises():
     k = parabolic.ParabolicKL(ptr, src, gnn)
     k.run(k.alloc("f64"), "f64")
     assert k.errors() & 128
-    # training_rows raises like np.linalg.inv (utils.py:277)
+    # training_rows turns the flag into the LinAlgError np.linalg.inv raises at the singular images (utils.py:285)
     with pytest.raises(np.linalg.LinAlgError):
         parabolic.training_rows_csr(ptr, src, gnn)
 
